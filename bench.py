@@ -10,6 +10,11 @@ One "step" = one EulerEDMSampler.sampler_step (reference sampling.py:78-89): mas
 50 images (2 x 25 frames, latent 4x72x128 = 576x1024 pixels) -> guider combine -> Euler update, on the 50-step
 sigma schedule. Inputs are synthetic and resident in HBM before the timed region; weights are random-init for the shipped
 1.65 B-parameter configuration (every tensor non-zero). Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line. --full adds everything else on top: the level-0 attention
+roofline (extra eager steps), the idle-stream host enqueue step, the side figures (unless --no-extras) and the CPU baseline (unless
+--no-cpu-baseline). --dump-outputs DIR writes the latents after the last timed step as DIR/latents.npy (float32); the inputs and
+weights are seeded, so equal arguments give equal inputs. K + W above the 50-step schedule restart the window from its initial noise.
 """
 import argparse
 import json
@@ -257,7 +262,7 @@ def fp16_side_figure(args):
     import subprocess
     env = dict(os.environ, VISTA_ACT_DTYPE="fp16")
     env.pop("VISTA_HIP_LIB", None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-extras"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-extras"]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -300,8 +305,10 @@ def main():
     ap.add_argument("--latent-h", type=int, default=72)
     ap.add_argument("--latent-w", type=int, default=128)
     ap.add_argument("--model-channels", type=int, default=320)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side figures (IdentityGuider N=25, GEMM rooflines, config-3 layout)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: attention roofline, idle-stream enqueue step, side figures, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the latents after the last timed step to DIR/latents.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side figures (IdentityGuider N=25, GEMM rooflines, config-3 layout)")
     ap.add_argument("--shard", choices=["hybrid", "frames"], default="hybrid")
     ap.add_argument("--plumbing-only", action="store_true", help="N > 1: rendezvous + partition/exchange check on the host, no GPU work")
     ap.add_argument("--graph", action="store_true", help="replay every step's UNet forward from one captured hipGraph (FusedLoop(graph=True)): the DEFAULT on one "
@@ -309,7 +316,7 @@ def main():
                     "ms per step, host enqueue 0.4 vs 10 ms); the level-0 attention launches of the roofline object are timed on two extra eager steps. N > 1: "
                     "refused over RCCL (capturing its collectives hangs on this stack, DESIGN section 6) unless VISTA_HIPGRAPH_RCCL=1")
     ap.add_argument("--one-stream", action="store_true", help="one GPU, graph replay: the step's two guidance halves as ONE forward of 50 images on one stream (the form of "
-                    "rounds 1-5) instead of two concurrent 25-image graphs on two streams (FusedLoop(cfg_streams=True), the default since round 6: -2.4 %)")
+                    "rounds 1-5) instead of two concurrent 25-image graphs on two streams (FusedLoop(cfg_streams=True), the default since round 6: -2.4 %%)")
     ap.add_argument("--eager", action="store_true", help="one GPU: enqueue every launch from Python each step instead of replaying the captured graph")
     ap.add_argument("--fp8", action="store_true",
                     help="BASELINE config 5, NOT the headline: FeedForward GEMMs AND the ResBlock convolutions in fp8 e4m3 (reported dtype says so)")
@@ -366,7 +373,7 @@ def main():
         # 'hybrid' (default): CFG halves x frame groups -- 8 GPUs = 2 x (7/6/6/6); 'frames': 4/3/3/3/3/3/3/3 (BASELINE config 3)
         shards = {args.shard: make_shard(T, world, rank, mode=args.shard, make_group=make_group)}
         other = "frames" if args.shard == "hybrid" else "hybrid"
-        if not args.no_extras and world % 2 == 0:  # odd worlds have one layout only
+        if args.full and not args.no_extras and world % 2 == 0:  # odd worlds have one layout only
             shards[other] = make_shard(T, world, rank, mode=other, make_group=make_group)
         # Plumbing pass BEFORE any model work: every collective signature of the sharded step on tiny device tensors, synchronised one by
         # one, so that a transport problem on a box this code has never seen is reported by name within seconds (vista_amd/parallel.py).
@@ -386,11 +393,12 @@ def main():
     x, sigmas, _, cond, uc = sampler.prepare_sampling_loop(noise, cu(w["c"]), cu(w["uc"]))
     sig = [float(s) for s in sigmas]
     nsteps = len(sig) - 1
-    assert args.warmup + args.steps <= nsteps, "at most 50 steps per window"
     fd = FusedDenoiser(den, OpenAIWrapper(net))
 
-    def timed_loop(shard, profile_attn, graph=False, settle=0):
-        """W warm-up + K timed steps of a fresh window; returns (seconds for K steps = MAX over ranks, host enqueue seconds, loop).
+    def timed_loop(shard, profile_attn, graph=False, settle=0, after=True, keep=False):
+        """W warm-up + K timed steps of a fresh window; returns (seconds for K steps = MAX over ranks, host enqueue seconds, loop, the whole
+        window's latents after the last timed step if `keep`). Step j runs schedule step j % 50: past its end the window restarts from its
+        initial noise. after: the idle-stream enqueue step and the attention-timing steps behind the timed region (--full).
         settle: extra untimed steps of a throw-away window first (a path that has just been switched on builds its weight packs in its first
         step and the allocator re-settles in the next one or two: config 5 measured 160.8 ms with one warm-up step, 151.7 with three)."""
         if settle:
@@ -400,15 +408,21 @@ def main():
             del tmp
         loop = FusedLoop(sampler, fd, x.float().clone(), cond, uc, w["cond_frame"].cuda(), w["cond_mask"].cuda(), True, sig, shard=shard,
                          graph=graph, cfg_streams=bool(graph and shard is None and not args.one_stream))
+        x_start = loop.xw.clone() if args.warmup + args.steps > nsteps else None
+
+        def step(j):
+            if j and j % nsteps == 0:
+                loop.xw.copy_(x_start)
+            loop.step(j % nsteps)
         for i in range(args.warmup):
-            loop.step(i)
+            step(i)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.warmup, args.warmup + args.steps):
-            loop.step(i)
+            step(i)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -419,11 +433,14 @@ def main():
             dist.all_reduce(tdt, op=dist.ReduceOp.MAX)
             dt = float(tdt.item())
         assert torch.isfinite(loop.xw).all(), "non-finite latents"
+        last = None
+        if keep:
+            last = (loop.xw if shard is None else shard.gather_frames(loop.xw)).float().cpu()
         # Host cost of enqueueing ONE step, measured OUTSIDE the timed region from an idle stream (sync, enqueue, stop the clock before the
         # next sync): inside the timed region the launch queue is full and the host clock only sees the GPU's back-pressure.
         t_enq = None
         nxt = args.warmup + args.steps
-        if nxt < nsteps:
+        if after and nxt < nsteps:
             t1 = time.perf_counter()
             loop.step(nxt)
             t_enq = time.perf_counter() - t1
@@ -433,21 +450,21 @@ def main():
                 dist.barrier()
         # The roofline kernel's launches are timed with HIP events (recorded on the launch stream, ops.attn_spatial) on up to two MORE steps of
         # the same window, right after the timed region: the timed region itself carries no profiling work
-        if profile_attn and not graph:
+        if after and profile_attn and not graph:
             ops.PROFILE_ATTN = []
             for i in range(nxt, min(nxt + 2, nsteps)):
                 loop.step(i)
             torch.cuda.synchronize()
             if dist is not None:
                 dist.barrier()
-        return dt, t_enq, loop
+        return dt, t_enq, loop, last
 
     main_key = args.shard if world > 1 else None
     shard = shards[main_key]
     # one GPU: graph replay unless --eager; N > 1: eager unless --graph (the sharded forward's capture has only ever run with the mock communicator)
     args.graph = (not args.eager) if world == 1 else bool(args.graph)
-    dt, t_enqueue, _ = timed_loop(shard, not args.graph, graph=args.graph)
-    if args.graph:  # a replayed graph runs no Python between launches: time the roofline kernel's launches on two eager steps of the same state
+    dt, t_enqueue, _, latents = timed_loop(shard, not args.graph, graph=args.graph, after=args.full, keep=bool(args.dump_outputs))
+    if args.graph and args.full:  # a replayed graph runs no Python between launches: time the roofline kernel's launches on two eager steps of the same state
         eager = FusedLoop(sampler, fd, x.float().clone(), cond, uc, w["cond_frame"].cuda(), w["cond_mask"].cuda(), True, sig, shard=shard, graph=False)
         eager.step(0)
         torch.cuda.synchronize()
@@ -457,7 +474,7 @@ def main():
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
-    prof, ops.PROFILE_ATTN = ops.PROFILE_ATTN, None
+    prof, ops.PROFILE_ATTN = ops.PROFILE_ATTN or [], None
     ms_per_step = dt * 1e3 / args.steps
     value = args.steps / dt
     full = (T, H, W, args.model_channels) == (25, 72, 128, 320)
@@ -510,11 +527,11 @@ def main():
         "step_mfma_frac": (FLOP_PER_STEP_CFG / (ms_per_step * 1e-3) / (MFMA_BF16_PEAK * world)) if full else None,
     }
     # ---- side figures (never `value`) ----
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         for key, sh in shards.items():  # the other multi-GPU layout, e.g. BASELINE config 3's 4/3/3/3/3/3/3/3 next to the hybrid default
             if key == main_key:
                 continue
-            dt2, _, _ = timed_loop(sh, False)
+            dt2 = timed_loop(sh, False)[0]
             res["config3_frames_layout" if key == "frames" else "hybrid_layout"] = {
                 "layout": layout(sh), "t_counts": sh.t_counts, "value": args.steps / dt2, "ms_per_step": dt2 * 1e3 / args.steps}
         if world == 1:
@@ -525,6 +542,7 @@ def main():
             maskf = w["cond_mask"].cuda().float()
 
             def ident_step(i):
+                i %= nsteps
                 s0, s1 = torch.full((n,), sig[i], device="cuda"), torch.full((n,), sig[i + 1], device="cuda")
                 return ident.sampler_step(s0, s1, fd, xi, cond, maskf, uc, 0.0)
             for i in range(args.warmup):
@@ -549,7 +567,7 @@ def main():
                 try:
                     for k in ("feedforward", "conv", "attention", "proj"):
                         _att.FP8[k] = True
-                    dt8, _, _ = timed_loop(None, False, settle=2)
+                    dt8 = timed_loop(None, False, settle=2)[0]
                     res["config5_fp8"] = {"value": args.steps / dt8, "unit": "steps/s", "ms_per_step": dt8 * 1e3 / args.steps,
                                           "note": "same step, fp8(e4m3) ResBlock convolutions, attention QK^T, and -- from block width 640 up, where fp8 still beats the bf16 kernels -- FeedForward GEMMs and attention-out projections; "
                                                   "parity: tests/test_fp8_gpu.py, tests/test_blocks_gpu.py"}
@@ -559,11 +577,15 @@ def main():
                 # The fp16-storage build (libvista_hip_f16.so: the reference's own autocast width, sample_utils.py:301-303) as a side
                 # figure: the same step in a process of its own (the storage type is fixed per process). Never `value`: BASELINE config 2 names bf16.
                 res["fp16_storage"] = fp16_side_figure(args)
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         res["cpu_baseline"] = cpu_baseline(net, T, H, W, seed=1) if full else None
     else:
         res["cpu_baseline"] = None
     if rank == 0:
+        if args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "latents.npy"), latents.numpy().astype(np.float32))
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()

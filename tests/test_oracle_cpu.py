@@ -101,32 +101,39 @@ def test_oracle_sampler_matches_reference_golden():
     assert torch.allclose(g["vanilla_noise_after"], w["noise"] * torch.sqrt(1.0 + O.edm_sigmas(3)[0] ** 2))
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference tree not mounted (GPU box)")
 def test_oracle_matches_live_reference_block():
-    """Live check of one full-width transformer + resblock pair against the reference modules themselves."""
-    import contextlib
-    import io
-    ref_shim.install()
-    with contextlib.redirect_stdout(io.StringIO()):
-        from vwm.modules.diffusionmodules.video_model import VideoResBlock
-        from vwm.modules.video_attention import SpatialVideoTransformer
-        rb = VideoResBlock(channels=320, emb_channels=1280, dropout=0.0, out_channels=640, video_kernel_size=[3, 1, 1],
-                           merge_strategy="learned_with_images").eval()
-        st = SpatialVideoTransformer(320, 5, 64, depth=1, context_dim=1024, use_linear=True, use_spatial_context=True, ff_in=True,
-                                     merge_strategy="learned_with_images", attn_mode="softmax-xformers", action_control=True).eval()
-    T, n, hh, ww = 3, 6, 4, 8
-    x = torch.randn(n, 320, hh, ww)
-    emb = torch.randn(n, 1280)
-    ctx = torch.randn(n, 1, synth.CTX_DIM)
+    """One full-width transformer + resblock pair against the reference modules' outputs on the same seeded weights and inputs
+    (tests/golden/ref_block.pt, oracle/make_golden_block.py) and, where the reference tree is mounted, against the live modules too."""
+    from oracle.make_golden_block import block_inputs
+    g = torch.load(os.path.join(GOLD, "ref_block.pt"))
+    T = g["T"]
+    x, emb, ctx = block_inputs(g["seed_x"])
+    live = {}
+    if ref_shim.available():
+        import contextlib
+        import io
+        ref_shim.install()
+        with contextlib.redirect_stdout(io.StringIO()):
+            from vwm.modules.diffusionmodules.video_model import VideoResBlock
+            from vwm.modules.video_attention import SpatialVideoTransformer
+            live["rb"] = VideoResBlock(channels=320, emb_channels=1280, dropout=0.0, out_channels=640, video_kernel_size=[3, 1, 1],
+                                       merge_strategy="learned_with_images").eval()
+            live["st"] = SpatialVideoTransformer(320, 5, 64, depth=1, context_dim=1024, use_linear=True, use_spatial_context=True, ff_in=True,
+                                                 merge_strategy="learned_with_images", attn_mode="softmax-xformers", action_control=True).eval()
     with torch.no_grad():
-        for mod, name in ((rb, "rb"), (st, "st")):
-            sd = synth.seeded_state_dict({k: tuple(v.shape) for k, v in mod.state_dict().items()}, 3)
-            mod.load_state_dict(sd)
+        for name in ("rb", "st"):
+            sd = synth.seeded_state_dict(g["shapes_" + name], g["seed_w"])
             sdp = {f"{name}.{k}": v for k, v in sd.items()}
             if name == "rb":
-                assert _rel(O.video_resblock(sdp, "rb", x, emb, T), mod(x, emb, T)) < 2e-4
+                got = O.video_resblock(sdp, "rb", x, emb, T)
             else:
-                assert _rel(O.spatial_video_transformer(sdp, "st", x, ctx, T, True), mod(x, ctx, None, T)) < 2e-4
+                got = O.spatial_video_transformer(sdp, "st", x, ctx, T, True)
+            assert _rel(got, g["out_" + name]) < 2e-4
+            if name in live:
+                mod = live[name]
+                assert {k: tuple(v.shape) for k, v in mod.state_dict().items()} == g["shapes_" + name]
+                mod.load_state_dict(sd)
+                assert _rel(got, mod(x, emb, T) if name == "rb" else mod(x, ctx, None, T)) < 2e-4
 
 
 def test_oracle_config1_miniature_matches_reference_golden():

@@ -218,7 +218,7 @@ def test_bench_gpus_2_end_to_end_dry_run_on_one_gpu():
     run in `data`); on a multi-GPU node the same command runs over RCCL."""
     import sys
     res = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "5", "--latent-h", "16",
-                "--latent-w", "32", "--model-channels", "64", "--no-cpu-baseline"], {"VISTA_DIST_BACKEND": "gloo", "VISTA_FORCE_DEVICE": "0"})
+                "--latent-w", "32", "--model-channels", "64", "--full", "--no-cpu-baseline"], {"VISTA_DIST_BACKEND": "gloo", "VISTA_FORCE_DEVICE": "0"})
     assert res["n_gpus"] == 2 and res["value"] > 0 and res["steps"] == 2
     assert res["config"]["t_counts"] == [5] and res["config"]["shard"] == "hybrid"
     assert res["config3_frames_layout"]["t_counts"] == [3, 2] and res["config3_frames_layout"]["value"] > 0

@@ -1,5 +1,5 @@
 """How much of the two-stream step do the two guidance halves really overlap?  Sweep over the dispatch intervals of a rocprofv3 kernel trace
-(`rocprofv3 --kernel-trace --output-format csv -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras`) inside the window
+(`rocprofv3 --kernel-trace --output-format csv -- python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extras`) inside the window
 spanned by the half graphs' level-0 attention launches (4500 workgroups of 256 threads, the longest launches of a half graph).
     python tools/stream_overlap.py <..._kernel_trace.csv>
 Prints the share of the window with 0 / 1 / >= 2 kernels in flight, and per kernel family the time it spends alone vs sharing the chip."""
