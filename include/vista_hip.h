@@ -40,9 +40,9 @@ typedef struct VkGemmDesc {
                             960), 7 = 256x320 eight-wave pipelined kernel (DENSE / CONV3X3 / TEMPORAL3 without halos x LINEAR, bf16 out,
                             DENSE x GEGLU; bitwise equal to 4). A variant that does not take the problem falls back to the launcher's choice.
                             Weight rows are zero-padded to max(ceil256(N), ceil320(N)) so every variant reads whole tiles.
-                            + 64 (with variant 0): apply the tail-split rule of vk_gemm_tail_split (an A/B option, off by default).
+                            + 64 (with variant 0): apply the tail-split rule of vk_gemm_tail_split (measured without gain; this bit is the only way to ask for it).
                             + 16: the four-wave pipelined 128x320 kernel, two workgroups per CU (DENSE x LINEAR / GEGLU, 16-bit out; bitwise equal
-                            to 7; an A/B option of round 6, off by default) wherever it takes the problem and leaves the row-sum slabs alone.        */
+                            to 7; measured slower, this bit is the only way to ask for it) wherever it takes the problem and leaves the row-sum slabs alone.        */
     const void* halo_prev; /* TEMPORAL3, frame-sharded runs: bf16 [clips][S][Cin] frame preceding / following the local frame range   */
     const void* halo_next; /* (from the neighbour rank); NULL = the conv's zero padding at the window ends                               */
     void* splitk_ws;     /* optional fp32 workspace for split-K of small-M, deep-K LINEAR problems (NULL = never split); must not be  */
@@ -273,7 +273,7 @@ int vk_groupnorm_finalize_partials(float* partial, float* sums, int32_t n_img, i
 /* ABI v7: the apply pass straight on stage-1 slots (`partial` as above, NOT consumed): every workgroup folds its image group's
  * frames_per_group * nchunks slots itself, in gn_finalize's summation order, so the output is bitwise that of vk_groupnorm_finalize_partials +
  * vk_groupnorm_apply_bf16 with one launch less (GroupNorm32 of openaimodel.py:195-199,227-234 = producer epilogue + ONE pass). Taken when
- * frames_per_group * nchunks <= vk_groupnorm_fold_max() (256; 0 when VISTA_GN_FOLD=0), else VK_EINVAL. Not for pixel-sharded norms (their raw
+ * frames_per_group * nchunks <= vk_groupnorm_fold_max() (256), else VK_EINVAL. Not for pixel-sharded norms (their raw
  * sums are all-reduced between the two stages). vk_groupnorm_silu_bf16 / _cat_bf16 apply the same rule to their own statistics pass. */
 int vk_groupnorm_fold_max(void);
 int vk_groupnorm_apply_partials_bf16(const void* x, void* y, const float* gamma, const float* beta, const float* partial, int32_t n_img,

@@ -499,7 +499,7 @@ def test_gemm_launch_rules_are_pinned():
 
 def test_gemm_tail_split_rule_is_pinned():
     """vk_gemm_tail_split: where vk_gemm_bf16 cuts a one-tile-per-workgroup launch into whole rounds + a 128x160 tail (round 5; measured without
-    gain and therefore OFF unless VISTA_GEMM_TAIL=<percent> or tile_cfg bit 6 asks for it -- which this test does). Host arithmetic only. Level 0 of the BASELINE window is 460800 rows = 1800 row tiles of 256: 7.03 rounds at N = 320 (tail = the last 8 row tiles), 21.09 at N = 960."""
+    gain and therefore OFF unless tile_cfg bit 6 asks for it -- which this test does). Host arithmetic only. Level 0 of the BASELINE window is 460800 rows = 1800 row tiles of 256: 7.03 rounds at N = 320 (tail = the last 8 row tiles), 21.09 at N = 960."""
     import ctypes as C
     from vista_amd import _lib, ops
     lib = _lib.load()
@@ -587,3 +587,70 @@ def test_gnstat_fit_rule_is_pinned():
     assert fit(50, 72, 128, 320, 320, m_begin=256, m_end=512) == 0
     assert fit(50, 72, 128, 320, 320, amode=ops.AMODE_DENSE) == 0  # (dense producers are not built with the emitting bodies)
     assert fit(50, 72, 128, 320, 320, gn_rows=0) == 0 and fit(50, 72, 128, 320, 320, gn_rows=9216 + 64) == 0
+
+
+def _gemm_plan_cases():
+    """The descriptor grid of tests/golden/gemm_plan.json, in a fixed order: every loader and epilogue at the BASELINE shapes (four levels x 50 / 25 / 7 / 4
+    images) x forced tile variants, tile_cfg bits 4 and 6 x the descriptor fields the launch rules read. Yields (label, VkGemmDesc)."""
+    import ctypes as C
+    from vista_amd import _lib, ops
+    ptr = C.c_void_p(4096)   # never dereferenced by the queries; aligned like a real tensor
+    D, C3, T3, C3D = ops.AMODE_DENSE, ops.AMODE_CONV3X3, ops.AMODE_TEMPORAL3, ops.AMODE_CONV3D
+    LIN, GEGLU, TRANS = ops.EPI_LINEAR, ops.EPI_GEGLU, ops.EPI_TRANS
+    options = {
+        "base": {}, "no_ws": {"splitk_ws": None, "splitk_ws_bytes": 0}, "rowstat": {"rowstat_out": ptr}, "f32": {"out_f32": 1}, "act": {"act": 1},
+        "res1": {"res1": ptr}, "res12": {"res1": ptr, "res2": ptr, "beta": 1.0}, "rowvec": {"rowvec": ptr},
+        "ln": {"ln_stats": ptr, "ln_colsum": ptr, "ln_parts": 2, "ln_eps": 1e-5}, "alt": {"alt_cols_from": 64}, "mx8": {"mx8_out": ptr, "mx8_scales": ptr},
+        "halo": {"halo_prev": ptr, "halo_next": ptr}, "gnstat": {"gnstat_out": ptr}, "rows": {"m_begin": 256}, "rows_head": {"m_begin": 0},
+    }
+    for lvl, (ch, H, W) in enumerate(((320, 72, 128), (640, 36, 64), (1280, 18, 32), (1280, 9, 16))):
+        S = H * W
+        kinds = [("proj", D, LIN, ch, ch), ("qkv", D, LIN, 3 * ch, ch), ("ff_out", D, LIN, ch, 4 * ch), ("geglu", D, GEGLU, 8 * ch, ch), ("trans", D, TRANS, ch, ch),
+                 ("conv", C3, LIN, ch, 9 * ch), ("conv_cat", C3, LIN, ch, 18 * ch), ("conv_t", T3, LIN, ch, 3 * ch), ("conv3d", C3D, LIN, 128 << (lvl & 1), 27 * 128)]
+        for n in (50, 25, 7, 4):
+            for kind, amode, epi, N, K in kinds:
+                for cfg in (0, 1, 2, 3, 4, 5, 6, 7, 16, 64):
+                    for opt, fields in options.items():
+                        if cfg in (1, 2, 3, 5, 6) and opt not in ("base", "no_ws", "rowstat"):
+                            continue
+                        d = _lib.VkGemmDesc()
+                        d.A = d.Wt = d.out = d.bias = ptr
+                        d.M, d.N, d.K, d.lda, d.ldc, d.alpha = n * S, N, K, K, (N // 2 if epi == GEGLU else N), 1.0
+                        d.ld_res1 = d.ld_res2 = d.ldv = N
+                        d.rows_per_vec, d.gn_rows = S, S
+                        d.amode, d.epi, d.tile_cfg = amode, epi, cfg
+                        d.splitk_ws, d.splitk_ws_bytes = ptr, 160 << 20
+                        d.S, d.T = S, (25 if n % 25 == 0 else n)
+                        if amode != D:
+                            d.Cin = K // {C3: 9, T3: 3, C3D: 27}[amode]
+                            d.H, d.Wd, d.Hout, d.Wout, d.stride, d.ups = H, W, H, W, 1, 1
+                        for k, v in fields.items():
+                            setattr(d, k, v)
+                        if opt == "mx8":
+                            d.mx8_cols, d.ld_mx8, d.ld_mx8s = (N // 320) * 320, N, N // 32
+                        if opt in ("rows", "rows_head"):
+                            d.m_end = d.M - 256
+                        yield f"L{lvl} n{n} {kind} cfg{cfg} {opt}", d
+
+
+def _gemm_plan_answers(lib):
+    import ctypes as C
+    return [[f(C.byref(d)) for f in (lib.vk_gemm_rowstat_parts, lib.vk_gemm_tile_choice, lib.vk_gemm_tail_split, lib.vk_gemm_gnstat_fit)]
+            for _, d in _gemm_plan_cases()]
+
+
+def test_gemm_plan_answers_match_the_recorded_launcher():
+    """The four launch queries answer from one launch plan (csrc/gemm.hip: plan_gemm). tests/golden/gemm_plan.json holds what the library answered
+    BEFORE the plan existed -- five hand-kept copies of the decision chain -- for every descriptor of _gemm_plan_cases(), recorded with no VISTA_* variable
+    set (tools/make_gemm_plan_golden.py, run against a build of that commit): [rowstat_parts, tile_choice, tail_split, gnstat_fit] per case. Every
+    answer must be reproduced exactly, errors included."""
+    from vista_amd import _lib
+    with open(os.path.join(os.path.dirname(__file__), "golden", "gemm_plan.json")) as f:
+        golden = json.load(f)
+    labels = [label for label, _ in _gemm_plan_cases()]
+    assert len(labels) == golden["cases"] == len(golden["answers"]) and labels[0] == golden["first"] and labels[-1] == golden["last"]
+    assert not any(k in os.environ for k in ("VISTA_GEMM_PIPE", "VISTA_GEMM_STREAM", "VISTA_TILE5_MAXK")), "recorded with the launch rules' default switches"
+    for storage in ("bf16", "fp16"):   # host arithmetic: the two builds of the sources answer alike
+        got = _gemm_plan_answers(_lib.load(storage))
+        wrong = [(label, g, w) for label, g, w in zip(labels, got, golden["answers"]) if g != w]
+        assert not wrong, f"{storage}: {len(wrong)} of {len(labels)} answers differ from the recorded launcher, first: {wrong[:5]}"

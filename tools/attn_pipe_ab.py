@@ -1,7 +1,7 @@
 """Same-box A/B of the level-0 / level-1 spatial attention in its PRODUCT form (q | k | v column blocks of one GEMM, V rows, pre-scaled query)
 across the launcher's VISTA_ATTN_PIPE modes: 0 = un-pipelined 8 x 64-row kernel (rounds 2-4), 1 = software-pipelined, four waves, two workgroups
-per CU, 2 = four waves, one workgroup per CU, 3 = eight waves. Every mode runs in its own process (the hook is read once), alternated; also
-checks every mode's output against mode 0.   usage: python tools/attn_pipe_ab.py [rounds] [modes, e.g. 0,1,3]"""
+per CU (default). Every mode runs in its own process (the hook is read once), alternated; also checks mode 1's output against mode 0.
+usage: python tools/attn_pipe_ab.py [rounds]"""
 import json
 import os
 import subprocess
@@ -42,7 +42,7 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--inner":
         return inner()
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    modes = [int(m) for m in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0, 1, 2, 3]
+    modes = [0, 1]
     best, sample = {}, {}
     for _ in range(rounds):
         for m in modes:

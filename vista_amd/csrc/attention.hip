@@ -678,8 +678,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_spatial_pipe_kernel(const uin
 // WIDE (default): 16-byte output stores (quad g of the upper half-wave swapped with quad g + 1 of the lower one, as the spatial kernels); needs
 // ldo % 8 == 0 and a 16-byte aligned `o`. WSYNC (measured, NOT the default): the V tile is wave-private, so the two workgroup barriers of an
 // iteration can be replaced by wave-local ordering (LDS executes a wave's instructions in order; the fences only pin the compiler).
-// VISTA_ATTN_T (launcher) selects: bit 0 = WSYNC, bit 1 = WIDE; bitwise the same results. Same box, alternated processes, ms per launch at
-// B = 2, T = 25 (tools/attn_t_ab.py, profiles/r05_attn_temporal_ab.txt):        level 0 (S 9216, 5 heads)   level 1 (2304, 10)   level 2 (576, 20)
+// The launcher instantiates WSYNC = false only (WIDE where the output rows allow it); bitwise the same results. Same box, alternated processes,
+// ms per launch at B = 2, T = 25 (profiles/r05_attn_temporal_ab.txt):        level 0 (S 9216, 5 heads)   level 1 (2304, 10)   level 2 (576, 20)
 //   0  barriers, 8-byte stores (rounds 1-4 of this repository)                  0.3152  3.74 TB/s            0.1586               0.0856
 //   1  wave-local sync, 8-byte stores                                            0.3387-0.3799               0.1707               0.0936   (slower: the barriers keep a
 //   2  barriers, 16-byte stores  <- default                                      0.2830  4.17 TB/s            0.1441               0.0796    workgroup's four problems -- four
@@ -1321,9 +1321,8 @@ static int attn_spatial_launch(const void* q, const void* k, const void* vt, voi
     static const float thr = [] { const char* e = getenv("VISTA_ATTN_RESCALE_THR"); return e ? (float)atof(e) : RESCALE_THR; }();  // tuning / A-B
     // long sequences: 8 waves x 64 query rows (512 per workgroup): every K / V^T fragment read feeds two MFMAs and the K/V^T stream
     // per FLOP halves again; medium ones 8 x 32; short ones 4 x 32 so the ragged last q-block wastes less (S = 144, 576 at the deep levels)
-    static const int qw_env = [] { const char* e = getenv("VISTA_ATTN_QW"); return e ? atoi(e) : 0; }();  // tuning / A-B: 1 or 2
-    int cls = S >= 4096 ? (qw_env == 1 ? 1 : 2) : (S >= 2048 ? (qw_env == 2 ? 2 : 1) : 0);
-    if (cls == 2 && qw_env == 0) {
+    int cls = S >= 4096 ? 2 : (S >= 2048 ? 1 : 0);
+    if (cls == 2) {
         // few images (one rank of a frame-sharded run): the 512-row workgroups run ONE per CU, so e.g. 7 images x 5 heads x 18 blocks = 630 of
         // them are 2.46 rounds = 3; 256-row workgroups (two per CU) finish the same work 8.5 % sooner (0.88 -> 0.805 ms), while at 8 / 13 / 50
         // images (2.8 / 4.6 / 17.6 rounds) the 512-row form stays 1-4 % ahead (profiles/r03_rank_proxy.txt)
@@ -1341,24 +1340,16 @@ static int attn_spatial_launch(const void* q, const void* k, const void* vt, voi
     if (pre && ldv <= 0) return VK_EINVAL;  // the pre-scaled form exists for the q | k | v column-block layout only
     if (pre) scale = 1.f / LOG2E;           // a score is already the base-2 exponent: scale_log2 = 1 for the general kernels below
     // Round 5: the software-pipelined zero-base kernel for long sequences made of whole workgroups of query rows (level 0: S = 9216).
-    // VISTA_ATTN_PIPE: 0 = off (A/B hook), 1 = four waves x 64 rows, two workgroups per CU, 2 = four waves, one workgroup per CU (one wave per
-    // SIMD), 3 = eight waves (two per SIMD in one workgroup).
-    static const int pipe_mode = [] { const char* e = getenv("VISTA_ATTN_PIPE"); return e ? atoi(e) : 1; }();
-    if (pre && pipe_mode > 0 && S >= 2048 && (ldo % 8) == 0 && (((size_t)o) & 15) == 0) {
-        const int rows = pipe_mode == 3 ? 512 : 256;
-        if (S % rows == 0) {
-            const long long nb = (long long)(S / rows) * n_img * heads;
-            if (nb > 0x7fffffffLL) return VK_EINVAL;
-#define ATTN_PIPE_LAUNCH(NW, ONE)                                                                                                             \
-    hipLaunchKernelGGL((attn_spatial_pipe_kernel<NW, ONE>), dim3((unsigned)nb), dim3(NW * 64), 0, (hipStream_t)stream_, (const uint16_t*)q,    \
-                       (const uint16_t*)k, (const uint16_t*)vt, (uint16_t*)o, n_img, heads, S, ldq, ldk, ldo, ldv)
-            if (pipe_mode == 3) ATTN_PIPE_LAUNCH(8, false);
-            else if (pipe_mode == 2) ATTN_PIPE_LAUNCH(4, true);
-            else ATTN_PIPE_LAUNCH(4, false);
-#undef ATTN_PIPE_LAUNCH
-            VK_CHECK_LAUNCH();
-            return VK_OK;
-        }
+    // Four waves x 64 rows, two workgroups per CU (one workgroup per CU and the eight-wave form measured slower: profiles/r05_attn_pipe.txt).
+    // VISTA_ATTN_PIPE=0: off (A/B hook).
+    static const bool pipe_on = [] { const char* e = getenv("VISTA_ATTN_PIPE"); return !e || atoi(e) != 0; }();
+    if (pre && pipe_on && S >= 2048 && (ldo % 8) == 0 && (((size_t)o) & 15) == 0 && S % 256 == 0) {
+        const long long nb = (long long)(S / 256) * n_img * heads;
+        if (nb > 0x7fffffffLL) return VK_EINVAL;
+        hipLaunchKernelGGL((attn_spatial_pipe_kernel<4, false>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream_, (const uint16_t*)q,
+                           (const uint16_t*)k, (const uint16_t*)vt, (uint16_t*)o, n_img, heads, S, ldq, ldk, ldo, ldv);
+        VK_CHECK_LAUNCH();
+        return VK_OK;
     }
     if (pre && cls == 2) {
         // zero-base kernel for the 512-row form only (241 VGPRs of its 256): 5.12 -> 4.95 ms per level-0 launch (1.06 -> 1.10 PFLOP/s). The
@@ -1405,15 +1396,11 @@ extern "C" int vk_attn_temporal_bf16(const void* qkv, void* o, int32_t B, int32_
     const long long cap = 256LL * 16;  // 16 workgroups per CU keeps plenty of loads in flight
     const int grid = (int)(want < cap ? want : cap);
     const int iters = (int)((want + grid - 1) / grid);
-    static const int mode_env = [] { const char* e = getenv("VISTA_ATTN_T"); return e ? atoi(e) : 2; }();   // A/B hook: bit 0 = wave-local sync, bit 1 = 16-byte stores (default: measured below)
-    int mode = mode_env & 3;
-    if ((ldo % 8) != 0 || (((size_t)o) & 15) != 0) mode &= 1;   // 16-byte stores need 16-byte aligned rows
-#define VK_ATTN_T(WS, WD) hipLaunchKernelGGL((attn_temporal_kernel<WS, WD>), dim3(grid), dim3(256), 0, (hipStream_t)stream_, (const uint16_t*)qkv, \
-                                             (uint16_t*)o, B, T, S, heads, ld, k_off, v_off, ldo, scale * LOG2E, nprob, iters)
-    if (mode == 3) VK_ATTN_T(true, true);
-    else if (mode == 2) VK_ATTN_T(false, true);
-    else if (mode == 1) VK_ATTN_T(true, false);
-    else VK_ATTN_T(false, false);
+    const bool wide = (ldo % 8) == 0 && (((size_t)o) & 15) == 0;   // 16-byte stores need 16-byte aligned rows
+#define VK_ATTN_T(WD) hipLaunchKernelGGL((attn_temporal_kernel<false, WD>), dim3(grid), dim3(256), 0, (hipStream_t)stream_, (const uint16_t*)qkv, \
+                                         (uint16_t*)o, B, T, S, heads, ld, k_off, v_off, ldo, scale * LOG2E, nprob, iters)
+    if (wide) VK_ATTN_T(true);
+    else VK_ATTN_T(false);
 #undef VK_ATTN_T
     VK_CHECK_LAUNCH();
     return VK_OK;

@@ -41,13 +41,13 @@
 // gemm_pipe.hip: the eight-wave pipelined 256x320 variant (tile_cfg 7); fit = 1 when it takes the problem
 extern "C" int vk_gemm_pipe_fit(const VkGemmDesc* d);
 extern "C" int vk_gemm_pipe_launch(const VkGemmDesc* d, void* stream, int ksplit);
-// gemm_pipe4.hip: the same kernel as four waves of 128 x 160 (round-6 experiment, measured 3-20 % behind: profiles/r06_gemm_pipe4.txt). NOT part of the
-// default build (VISTA_BUILD_PIPE4=1 python -m vista_amd.build adds it): a weak reference, resolved only in an A/B library
-extern "C" int vk_gemm_pipe4_launch(const VkGemmDesc* d, void* stream, int ksplit) __attribute__((weak));
 extern "C" int vk_gemm_pipe_gnstat_ok(const VkGemmDesc* d, int ksplit);
-// gemm_pipe2.hip: the four-wave pipelined 128x320 variant, two workgroups per CU (tile_cfg bit 4 / VISTA_GEMM_PIPE2: an A/B option, off by default)
+// gemm_pipe2.hip: the four-wave pipelined 128x320 variant, two workgroups per CU (tile_cfg bit 4 asks for it: measured slower, profiles/r06_gemm_pipe2.txt)
 extern "C" int vk_gemm_pipe2_fit(const VkGemmDesc* d);
 extern "C" int vk_gemm_pipe2_launch(const VkGemmDesc* d, void* stream);
+// gemm_stream.hip: the weight-stationary streaming kernel for the level-0 K = 320 projections (0 = does not take this problem)
+extern "C" int vk_gemm_stream_fit(const VkGemmDesc* d);
+extern "C" int vk_gemm_stream_launch(const VkGemmDesc* d, void* stream);
 
 namespace {
 
@@ -433,12 +433,16 @@ int launch_cfg(const VkGemmDesc* d, hipStream_t stream, int ksplit = 1) {
     }
     hipLaunchKernelGGL((gemm_kernel<AMODE, EPI, OUT_F32, WM, WN, FM, FN>), dim3(grid), dim3(WM * WN * 64), 0, stream, desc, ksplit);
     VK_CHECK_LAUNCH();
-    if (ksplit > 1) {
-        const long long quads = (long long)d->M * (d->N >> 2);
-        const int grid = (int)((quads + 255) / 256 < 4096 ? (quads + 255) / 256 : 4096);
-        hipLaunchKernelGGL((splitk_finish_kernel<OUT_F32>), dim3(grid), dim3(256), 0, stream, desc, ksplit);
-        VK_CHECK_LAUNCH();
-    }
+    return VK_OK;   // (ksplit > 1: run_plan adds the finishing pass)
+}
+
+// The finishing pass of a split-K launch, whichever kernel wrote the partials
+int launch_splitk_finish(const VkGemmDesc* d, hipStream_t stream, int ksplit) {
+    const long long quads = (long long)d->M * (d->N >> 2);
+    const int grid = (int)((quads + 255) / 256 < 4096 ? (quads + 255) / 256 : 4096);
+    if (d->out_f32) hipLaunchKernelGGL((splitk_finish_kernel<true>), dim3(grid), dim3(256), 0, stream, *d, ksplit);
+    else hipLaunchKernelGGL((splitk_finish_kernel<false>), dim3(grid), dim3(256), 0, stream, *d, ksplit);
+    VK_CHECK_LAUNCH();
     return VK_OK;
 }
 
@@ -450,13 +454,14 @@ struct TileChoice { int cfg, ksplit; };  // cfg: 1 = 128x128, 2 = 256x128, 3 = 2
 
 // cfg 5 exists for DENSE / LINEAR / bf16-out GEMMs only (the HBM-bound K = C projections it is meant for): everything else maps it to 4
 inline bool cfg5_ok(const VkGemmDesc* d) { return d->amode == AMODE_DENSE && d->epi == EPI_LINEAR && !d->out_f32 && (d->N % 160) == 0; }
-inline TileChoice choose_tile(const VkGemmDesc* d) {
+// rowstat / gnstat: the launch emits row sums / GroupNorm statistics of its output (the queries ask before the caller has a buffer to point at)
+inline TileChoice choose_tile(const VkGemmDesc* d, bool rowstat, bool gnstat) {
     static const int tile5_max_k = [] { const char* e = getenv("VISTA_TILE5_MAXK"); return e ? atoi(e) : TILE5_MAX_K_DEFAULT; }();
     const int amode = d->amode, epi = d->epi;
     const int force = d->tile_cfg & 7;  // 0 = auto (tests / tuning force a variant)
     // tile_cfg bit 4 (alone): the two-per-CU pipelined kernel is asked for. Where it takes the problem the answer is the 320-column, two-wave-column
-    // geometry of variant 7 without K slices (row-sum slabs, vk_gemm_tile_choice), whatever the size rules below would pick; launch() then routes it.
-    if ((d->tile_cfg & 16) && force == 0 && vk_gemm_pipe2_fit(d)) return {7, 1};
+    // geometry of variant 7 without K slices (row-sum slabs, vk_gemm_tile_choice), whatever the size rules below would pick; plan_gemm then routes it.
+    if ((d->tile_cfg & 16) && force == 0 && !gnstat && vk_gemm_pipe2_fit(d)) return {7, 1};
     int cfg = force;
     if (d->mx8_out) cfg = 4;  // MX-fp8 output lives in the LDS-staged epilogue of whole 320-column tiles (validate() checked N and mx8_cols)
     if (cfg == 5 && !cfg5_ok(d)) cfg = 4;
@@ -508,7 +513,7 @@ inline TileChoice choose_tile(const VkGemmDesc* d) {
     // tiles x slices ~ one full round of CUs; fp32 partials go to the caller's workspace and a finishing pass applies the epilogue.
     // Not combined with the LayerNorm fold / row-sum emission (their epilogues need the finished accumulator in registers).
     int ksplit = 1;
-    if (epi == EPI_LINEAR && force == 0 && d->splitk_ws && cfg != 4 && cfg != 3 && cfg != 5 && !d->ln_stats && !d->rowstat_out && !d->act && !d->alt_cols_from &&
+    if (epi == EPI_LINEAR && force == 0 && d->splitk_ws && cfg != 4 && cfg != 3 && cfg != 5 && !d->ln_stats && !rowstat && !d->act && !d->alt_cols_from &&
         d->m_begin == 0 && d->m_end == d->M) {   // (the finishing pass walks all M rows: no split-K on a row range)
         const bool ok320s = (amode != AMODE_CONV3D) && (d->N % 320 == 0);
         const int bn = ok320s ? 320 : 256;
@@ -545,18 +550,17 @@ inline void tile_geometry(int cfg, int& bn, int& wn) {
 // Tail split of a one-tile-per-workgroup launch of the 256x320 pipelined kernel (LINEAR epilogue). With one 162 KB workgroup per CU the launch
 // takes ceil(tiles / 256) tile times, and the BASELINE shapes leave the last round almost empty: level 0 is 460800 rows = 1800 row tiles =
 // 7.03 rounds at N = 320 (eight tiles keep the chip for an eighth round: 12 % of the launch) and 21.09 at N = 960. When the last round would
-// be filled to at most VISTA_GEMM_TAIL percent, the whole rounds run as rows [m_begin, m_split) on the pipelined kernel and the remaining
+// be filled to at most 40 percent, the whole rounds run as rows [m_begin, m_split) on the pipelined kernel and the remaining
 // rows [m_split, m_end) as a second launch of 128x160 tiles (four waves, two workgroups per CU: a quarter of the work per workgroup, all of
 // them resident at once) -- the same MFMA sequence per output element, the same row-sum slabs (160 columns each): bitwise the same result
 // as the single launch (tests/test_kernels_gpu.py::test_gemm_tail_split_and_row_ranges_are_bitwise). Returns the split row, 0 = no split.
 // MEASURED (round 5, profiles/r05_negative_results.txt section 1) and NOT adopted: the split changes nothing (level-0 conv3x3 0.7239 vs 0.7245 ms,
 // q|k|v 0.4602 vs 0.4626, temporal conv 0.318 vs 0.306; step 169.4 vs 169.5 ms). The eight tiles of the "eighth round" do not cost a round: alone
 // on the chip they run ~2.4x faster than a tile among 255 others (no HBM / L2 contention, and the clock is no longer held down by the power
-// of 256 busy CUs), which is about what the extra launch costs. The rule stays available as VISTA_GEMM_TAIL=<percent> (A/B hook), default off.
+// of 256 busy CUs), which is about what the extra launch costs. Only tile_cfg bit 6 asks for the rule (tests).
 inline int tail_split_row(const VkGemmDesc* d, const TileChoice& t) {
-    static const int env_pct = [] { const char* e = getenv("VISTA_GEMM_TAIL"); return e ? atoi(e) : 0; }();   // OFF by default: see the note above
-    const int max_pct = (d->tile_cfg & 64) ? 40 : env_pct;   // tile_cfg bit 6: the caller asks for the split rule (tests)
-    if (max_pct <= 0 || t.cfg != 7 || t.ksplit != 1 || (d->tile_cfg & 7) != 0 || d->epi != EPI_LINEAR || d->out_f32 || (d->N % 320) != 0) return 0;
+    const int max_pct = 40;
+    if (!(d->tile_cfg & 64) || t.cfg != 7 || t.ksplit != 1 || (d->tile_cfg & 7) != 0 || d->epi != EPI_LINEAR || d->out_f32 || (d->N % 320) != 0) return 0;
     const int rows = d->m_end - d->m_begin;
     const long long tilesN = d->N / 320, tilesM = (rows + 255) / 256, ntiles = tilesM * tilesN;
     const long long full = ntiles / 256, rem = ntiles % 256;
@@ -569,66 +573,107 @@ inline int tail_split_row(const VkGemmDesc* d, const TileChoice& t) {
     return m_split;
 }
 
-// The two-per-CU pipelined kernel (gemm_pipe2.hip) instead of the launcher's choice `t`? Only where it leaves the row-sum slab geometry alone (the
-// 320-column variants 4 / 5 / 7 all write one slab per 160 columns, as it does; GEGLU launches emit none) and never for a split-K launch.
-// tile_cfg bit 4 forces it (tests / probes); VISTA_GEMM_PIPE2 = 1 (LINEAR) | 2 (GEGLU) | 3 (both) turns it on for whole-round problems with
-// K <= VISTA_PIPE2_MAXK (default 1280). Off by default: profiles/r06_gemm_pipe2.txt.
-inline bool pipe2_wanted(const VkGemmDesc* d, const TileChoice& t) {
-    static const int mode = [] { const char* e = getenv("VISTA_GEMM_PIPE2"); return e ? atoi(e) : 0; }();
-    static const int maxk = [] { const char* e = getenv("VISTA_PIPE2_MAXK"); return e ? atoi(e) : 1280; }();
-    const bool forced = (d->tile_cfg & 16) != 0;
-    if (!forced && !(mode & (d->epi == EPI_GEGLU ? 2 : 1))) return false;
-    if (t.ksplit != 1 || d->amode != AMODE_DENSE || d->out_f32) return false;
+// The two-per-CU pipelined kernel (gemm_pipe2.hip) instead of the tile choice `t`? Only when tile_cfg bit 4 asks for it (tests / probes; measured
+// slower: profiles/r06_gemm_pipe2.txt), only where it leaves the row-sum slab geometry alone (the 320-column variants 4 / 5 / 7 all write one slab
+// per 160 columns, as it does; GEGLU launches emit none), never for a split-K launch, and never for one that emits GroupNorm statistics.
+inline bool pipe2_wanted(const VkGemmDesc* d, const TileChoice& t, bool gnstat) {
+    if (!(d->tile_cfg & 16) || gnstat || t.ksplit != 1 || d->amode != AMODE_DENSE || d->out_f32) return false;
     if (d->epi == EPI_LINEAR && t.cfg != 4 && t.cfg != 5 && t.cfg != 7) return false;
-    if (!forced) {
-        if ((d->tile_cfg & 7) != 0 || d->K > maxk) return false;
-        const long long tiles = (long long)((d->m_end - d->m_begin + 127) / 128) * (d->N / 320);
-        if (tiles < 512) return false;   // less than one round of two workgroups per CU: the small-problem rules stay
-    }
     return vk_gemm_pipe2_fit(d) != 0;
 }
 
+// ---- the launch plan: everything that decides which kernels a descriptor runs on, for the queries and for vk_gemm_bf16 alike ----
+enum GemmFamily { FAM_STREAM, FAM_PIPE2, FAM_PIPE, FAM_TILED };   // gemm_stream.hip, gemm_pipe2.hip, gemm_pipe.hip, gemm_kernel above
+struct GemmPlan {
+    int family;
+    int cfg;            // tile variant (TileChoice; 6 = the streaming kernel)
+    int ksplit;         // K slices; > 1: fp32 partials + the finishing pass
+    int tail_row;       // FAM_PIPE: rows from here on run as a second launch of 128x160 tiles (tail_split_row); 0 = one launch
+    int rowstat_slabs;  // row-sum slabs a rowstat_out launch writes
+    int gnstat_slots;   // 64-float slots of GroupNorm statistics a gnstat_out launch can emit; 0 = it cannot
+};
+
+// `d`: validated, row range normalised; a forced variant 6 that the streaming kernel does not take is stripped from it (the launcher's own
+// choice then). rowstat / gnstat: whether the launch emits row sums / GroupNorm statistics -- inputs of their own because the queries are
+// asked BEFORE the caller has a buffer whose pointer the descriptor could carry.
+GemmPlan plan_gemm(VkGemmDesc& d, bool rowstat, bool gnstat) {
+    static const bool stream_on = [] { const char* e = getenv("VISTA_GEMM_STREAM"); return !e || atoi(e) != 0; }();   // A/B hook: 0 = tiled kernels only
+    const int force = d.tile_cfg & 7;
+    // the streaming kernel: whole row range, not next to tile_cfg bit 4, and on its own choice (force == 0) never for a row-sum emitting launch
+    if (d.m_begin == 0 && d.m_end == d.M && !(d.tile_cfg & 16) && (force == 6 || (stream_on && !rowstat))) {
+        if (const int fit = vk_gemm_stream_fit(&d)) return {FAM_STREAM, 6, 1, 0, d.N / (32 * fit), 0};   // one slab per column tile: the workgroup combines its waves' row sums
+    }
+    if (force == 6) d.tile_cfg &= ~7;
+    const TileChoice t = choose_tile(&d, rowstat, gnstat);
+    GemmPlan p{FAM_TILED, t.cfg, t.ksplit, 0, 0, 0};
+    if (pipe2_wanted(&d, t, gnstat)) p.family = FAM_PIPE2;
+    else if (t.cfg == 7) p.family = FAM_PIPE;
+    if (p.family == FAM_PIPE) p.tail_row = tail_split_row(&d, t);
+    int bn, wn;
+    tile_geometry(t.cfg, bn, wn);   // (the tail launch and the two-per-CU kernel write the slabs of the variant they stand in for)
+    p.rowstat_slabs = ((d.N + bn - 1) / bn) * wn;
+    if (p.family == FAM_PIPE && p.ksplit == 1 && p.tail_row == 0 && !rowstat && vk_gemm_pipe_gnstat_ok(&d, 1)) p.gnstat_slots = d.M / 64;
+    return p;
+}
+
+// (loader, epilogue, output type, tile variant) -> gemm_kernel instantiation: template dispatch only, the plan has decided everything else
 template <int AMODE, int EPI, bool OUT_F32>
-int launch(const VkGemmDesc* d, hipStream_t stream) {
-    const TileChoice t = choose_tile(d);
-    if constexpr (AMODE == AMODE_DENSE && (EPI == EPI_LINEAR || EPI == EPI_GEGLU) && !OUT_F32) {
-        if (pipe2_wanted(d, t)) return vk_gemm_pipe2_launch(d, stream);
-    }
-    if constexpr (EPI == EPI_LINEAR && !OUT_F32 && (AMODE == AMODE_DENSE || AMODE == AMODE_CONV3X3 || AMODE == AMODE_TEMPORAL3)) {
-        if (const int m_split = tail_split_row(d, t)) {
-            VkGemmDesc head = *d, tail = *d;
-            head.m_end = m_split;
-            tail.m_begin = m_split;
-            const int rc = vk_gemm_pipe_launch(&head, stream, 1);
-            if (rc != VK_OK) return rc;
-            return launch_cfg<AMODE, EPI, OUT_F32, 4, 1, 1, 5>(&tail, stream);
-        }
-    }
-    if constexpr (AMODE == AMODE_DENSE && EPI == EPI_LINEAR && !OUT_F32) {
-        if (t.cfg == 5) return launch_cfg<AMODE, EPI, OUT_F32, 4, 1, 1, 5>(d, stream);  // 128x160: four 32x160 wave tiles, two workgroups per CU
+int launch(const VkGemmDesc* d, hipStream_t stream, int cfg, int ksplit) {
+    if constexpr (EPI == EPI_LINEAR && !OUT_F32 && AMODE != AMODE_CONV3D) {
+        // 128x160: four 32x160 wave tiles, two workgroups per CU (DENSE: variant 5; the convolution loaders: the tail launch of a split only)
+        if (cfg == 5) return launch_cfg<AMODE, EPI, OUT_F32, 4, 1, 1, 5>(d, stream);
     }
     if constexpr (AMODE != AMODE_CONV3D) {
         // 256x320 as sixteen 32x160 wave tiles (<= 128 VGPRs with single-buffered fragments): +4-11 % over eight 64x160 tiles
         // on the projections and the implicit-GEMM convs (tools/gemm_sweep.py), for the same reason as the 256x256 case below
-        if (t.cfg == 7) {   // eight 64x160 wave tiles, pipelined K-step (gemm_pipe.hip); VISTA_GEMM_PIPE4: its four-wave build (gemm_pipe4.hip, A/B hook:
-            // 1 = every launch of this variant, 2 = the convolution loaders only, 3 = the dense loader only)
-            static const int pipe4 = [] { const char* e = getenv("VISTA_GEMM_PIPE4"); return e ? atoi(e) : 0; }();
-            const bool w4 = vk_gemm_pipe4_launch != nullptr && (pipe4 == 1 || (pipe4 == 2 && AMODE != AMODE_DENSE) || (pipe4 == 3 && AMODE == AMODE_DENSE));
-            const int rc = w4 ? vk_gemm_pipe4_launch(d, stream, t.ksplit) : vk_gemm_pipe_launch(d, stream, t.ksplit);
-            if (rc != VK_OK || t.ksplit == 1) return rc;
-            const long long quads = (long long)d->M * (d->N >> 2);   // the split-K finishing pass, as launch_cfg's
-            const int grid = (int)((quads + 255) / 256 < 4096 ? (quads + 255) / 256 : 4096);
-            hipLaunchKernelGGL((splitk_finish_kernel<OUT_F32>), dim3(grid), dim3(256), 0, stream, *d, t.ksplit);
-            VK_CHECK_LAUNCH();
-            return VK_OK;
-        }
-        if (t.cfg == 4) return launch_cfg<AMODE, EPI, OUT_F32, 8, 2, 1, 5>(d, stream, t.ksplit);
+        if (cfg == 4) return launch_cfg<AMODE, EPI, OUT_F32, 8, 2, 1, 5>(d, stream, ksplit);
     }
     // 256x256 runs as SIXTEEN waves (4 per SIMD, 64x64 wave tiles, <= 128 VGPRs): same bytes per FLOP as the 8-wave layout, but twice
     // the waves to cover LDS-read latency, DMA issue and the per-K-step barrier (+5-10 % on GEGLU and the N % 320 != 0 projections).
-    if (t.cfg == 3) return launch_cfg<AMODE, EPI, OUT_F32, 4, 4, 2, 2>(d, stream, t.ksplit);
-    if (t.cfg == 2) return launch_cfg<AMODE, EPI, OUT_F32, 4, 4, 2, 1>(d, stream);  // 256x128, sixteen 64x32 wave tiles
+    if (cfg == 3) return launch_cfg<AMODE, EPI, OUT_F32, 4, 4, 2, 2>(d, stream, ksplit);
+    if (cfg == 2) return launch_cfg<AMODE, EPI, OUT_F32, 4, 4, 2, 1>(d, stream);  // 256x128, sixteen 64x32 wave tiles
     return launch_cfg<AMODE, EPI, OUT_F32, 4, 2, 1, 2>(d, stream);  // 128x128 as eight 32x64 wave tiles, two workgroups per CU
+}
+
+int launch_tiled(const VkGemmDesc* d, hipStream_t stream, int cfg, int ksplit) {
+    const bool f32 = d->out_f32 != 0;
+    switch (d->epi) {
+        case EPI_LINEAR:
+            if (d->amode == AMODE_DENSE) return f32 ? launch<AMODE_DENSE, EPI_LINEAR, true>(d, stream, cfg, ksplit) : launch<AMODE_DENSE, EPI_LINEAR, false>(d, stream, cfg, ksplit);
+            if (d->amode == AMODE_CONV3X3) return f32 ? launch<AMODE_CONV3X3, EPI_LINEAR, true>(d, stream, cfg, ksplit) : launch<AMODE_CONV3X3, EPI_LINEAR, false>(d, stream, cfg, ksplit);
+            if (d->amode == AMODE_TEMPORAL3) return f32 ? launch<AMODE_TEMPORAL3, EPI_LINEAR, true>(d, stream, cfg, ksplit) : launch<AMODE_TEMPORAL3, EPI_LINEAR, false>(d, stream, cfg, ksplit);
+            if (d->amode == AMODE_CONV3D) return f32 ? launch<AMODE_CONV3D, EPI_LINEAR, true>(d, stream, cfg, ksplit) : launch<AMODE_CONV3D, EPI_LINEAR, false>(d, stream, cfg, ksplit);
+            return VK_EINVAL;
+        case EPI_GEGLU: return launch<AMODE_DENSE, EPI_GEGLU, false>(d, stream, cfg, ksplit);
+        case EPI_TRANS: return launch<AMODE_DENSE, EPI_TRANS, false>(d, stream, cfg, ksplit);
+    }
+    return VK_EINVAL;
+}
+
+// what the epilogues ask of a descriptor beyond validate() (vk_gemm_bf16 only: the queries answer for the shape as given)
+inline int check_epilogue(const VkGemmDesc* d) {
+    if (d->epi == EPI_LINEAR) return (d->ldc % 4) != 0 ? VK_EINVAL : VK_OK;
+    if (d->amode != AMODE_DENSE || d->out_f32) return VK_EINVAL;
+    if (d->epi == EPI_GEGLU) return (d->N % 32) != 0 ? VK_EINVAL : VK_OK;  // whole [16 value | 16 gate] fragments
+    if (d->epi == EPI_TRANS) return (d->S <= 0 || (d->S % 4) != 0) ? VK_EINVAL : VK_OK;
+    return VK_EINVAL;
+}
+
+int run_plan(const VkGemmDesc* d, const GemmPlan& p, hipStream_t stream) {
+    if (p.family == FAM_STREAM) return vk_gemm_stream_launch(d, stream);
+    int rc = check_epilogue(d);
+    if (rc != VK_OK) return rc;
+    if (p.family == FAM_PIPE2) return vk_gemm_pipe2_launch(d, stream);
+    if (p.family == FAM_PIPE && p.tail_row) {
+        VkGemmDesc head = *d, tail = *d;
+        head.m_end = p.tail_row;
+        tail.m_begin = p.tail_row;
+        rc = vk_gemm_pipe_launch(&head, stream, 1);
+        return rc != VK_OK ? rc : launch_tiled(&tail, stream, 5, 1);
+    }
+    rc = (p.family == FAM_PIPE) ? vk_gemm_pipe_launch(d, stream, p.ksplit) : launch_tiled(d, stream, p.cfg, p.ksplit);
+    if (rc != VK_OK || p.ksplit == 1) return rc;
+    return launch_splitk_finish(d, stream, p.ksplit);
 }
 
 inline int validate(const VkGemmDesc* d) {
@@ -661,100 +706,61 @@ inline int validate(const VkGemmDesc* d) {
     return VK_OK;
 }
 
+// validate, normalise the row range into `q`, plan: the whole preamble of every entry point below. rowstat / gnstat: plan as emitting although the
+// descriptor carries no pointer yet (a pointer that is set always counts)
+int plan_for(const VkGemmDesc* d, VkGemmDesc& q, bool rowstat, bool gnstat, GemmPlan& p) {
+    const int rc = validate(d);
+    if (rc != VK_OK) return rc;
+    q = *d;
+    norm_row_range(q);   // m_end = M unless the caller asked for a row range (validate() checked it)
+    p = plan_gemm(q, rowstat || q.rowstat_out != nullptr, gnstat || q.gnstat_out != nullptr);
+    return VK_OK;
+}
+
 }  // namespace
 
-// gemm_stream.hip: the weight-stationary streaming kernel for the level-0 K = 320 projections (0 = does not take this problem)
-extern "C" int vk_gemm_stream_fit(const VkGemmDesc* d);
-extern "C" int vk_gemm_stream_launch(const VkGemmDesc* d, void* stream);
-static int stream_fit(const VkGemmDesc* d) {
-    static const bool on = [] { const char* e = getenv("VISTA_GEMM_STREAM"); return !e || atoi(e) != 0; }();   // A/B hook: 0 = tiled kernels only
-    if (d->tile_cfg & 16) return 0;   // (the two-per-CU pipelined kernel was asked for)
-    return (on || (d->tile_cfg & 7) == 6) ? vk_gemm_stream_fit(d) : 0;
-}
-
+// Row-sum slabs the launch of `d` writes. Asked BEFORE the caller can set rowstat_out (the buffer is sized from the answer): planned as emitting.
+// (Round 4 regression: the streaming K = 320 kernel, which is not chosen for row-sum emitting launches, answered with its 1 slab.)
 extern "C" int vk_gemm_rowstat_parts(const VkGemmDesc* d) {
-    const int rc = validate(d);
+    VkGemmDesc q;
+    GemmPlan p;
+    const int rc = plan_for(d, q, true, false, p);
     if (rc != VK_OK) return rc;
-    if (d->epi != EPI_LINEAR || d->out_f32) return VK_EINVAL;
-    VkGemmDesc q = *d;
-    norm_row_range(q);
-    q.rowstat_out = (float*)1;  // what the launcher will see (callers size the buffer from this answer BEFORE they can set the pointer): the
-                                // streaming kernel is not chosen on its own for a row-sum emitting launch, and such a launch is never split-K
-    if (const int fit = (q.m_begin == 0 && q.m_end == q.M) ? stream_fit(&q) : 0) return d->N / (32 * fit);  // one slab per column tile: the workgroup combines its waves' row sums
-    if ((q.tile_cfg & 7) == 6) q.tile_cfg &= ~7;
-    const TileChoice t = choose_tile(&q);
-    int bn, wn;
-    tile_geometry(t.cfg, bn, wn);
-    return ((d->N + bn - 1) / bn) * wn;
+    return (q.epi != EPI_LINEAR || q.out_f32) ? VK_EINVAL : p.rowstat_slabs;
 }
 
-// The launcher's decision for `d`, without launching: (block-tile variant 1..5) * 16 + K slices. Pure host arithmetic (the CPU test-suite pins
+// The launcher's decision for `d`, without launching: (block-tile variant 1..7) * 16 + K slices. Pure host arithmetic (the CPU test-suite pins
 // the launch rules with it); negative = the error vk_gemm_bf16 would return.
 extern "C" int vk_gemm_tile_choice(const VkGemmDesc* d) {
-    const int rc = validate(d);
-    if (rc != VK_OK) return rc;
-    VkGemmDesc q = *d;
-    norm_row_range(q);
-    if (q.m_begin == 0 && q.m_end == q.M && stream_fit(d)) return 6 * 16 + 1;
-    if ((q.tile_cfg & 7) == 6) q.tile_cfg &= ~7;
-    const TileChoice t = choose_tile(&q);
-    return t.cfg * 16 + t.ksplit;
+    VkGemmDesc q;
+    GemmPlan p;
+    const int rc = plan_for(d, q, false, false, p);
+    return rc != VK_OK ? rc : p.cfg * 16 + p.ksplit;
 }
 
 // The row at which vk_gemm_bf16 would split `d` into a pipelined launch of whole rounds + a 128x160 tail launch (tail_split_row), 0 = one launch;
 // negative = the error vk_gemm_bf16 would return. Pure host arithmetic.
 extern "C" int vk_gemm_tail_split(const VkGemmDesc* d) {
-    const int rc = validate(d);
-    if (rc != VK_OK) return rc;
-    VkGemmDesc q = *d;
-    norm_row_range(q);
-    if (q.m_begin == 0 && q.m_end == q.M && stream_fit(d)) return 0;
-    if ((q.tile_cfg & 7) == 6) q.tile_cfg &= ~7;
-    if (q.epi != EPI_LINEAR || q.out_f32 || q.amode == AMODE_CONV3D) return 0;
-    return tail_split_row(&q, choose_tile(&q));
+    VkGemmDesc q;
+    GemmPlan p;
+    const int rc = plan_for(d, q, false, false, p);
+    return rc != VK_OK ? rc : p.tail_row;
 }
 
-// ABI v6: can the launch vk_gemm_bf16 would make for `d` emit the GroupNorm statistics of its output (VkGemmDesc.gnstat_out)? The answer is formed
-// from the launcher's own decision chain (streaming kernel, tile choice, K slices, tail split) -- none of which reads gnstat_out, so the launch
-// that follows with the pointer set takes the same kernel; vk_gemm_bf16 re-checks and refuses rather than dropping the statistics.
+// ABI v6: can the launch vk_gemm_bf16 would make for `d` emit the GroupNorm statistics of its output (VkGemmDesc.gnstat_out)? Asked before the
+// caller has the buffer: planned as emitting. The answer is the slot count, 0 = it cannot; vk_gemm_bf16 refuses rather than dropping the statistics.
 extern "C" int vk_gemm_gnstat_fit(const VkGemmDesc* d) {
-    const int rc = validate(d);
-    if (rc != VK_OK) return rc;
-    VkGemmDesc q = *d;
-    norm_row_range(q);
-    if (q.epi != EPI_LINEAR || q.out_f32 || (q.amode != AMODE_CONV3X3 && q.amode != AMODE_TEMPORAL3)) return 0;
-    if (q.m_begin == 0 && q.m_end == q.M && stream_fit(d)) return 0;
-    if ((q.tile_cfg & 7) == 6) q.tile_cfg &= ~7;
-    const TileChoice t = choose_tile(&q);
-    if (t.cfg != 7 || t.ksplit != 1 || tail_split_row(&q, t) != 0) return 0;
-    return vk_gemm_pipe_gnstat_ok(&q, 1) ? q.M / 64 : 0;
+    VkGemmDesc q;
+    GemmPlan p;
+    const int rc = plan_for(d, q, false, true, p);
+    return rc != VK_OK ? rc : p.gnstat_slots;
 }
 
-extern "C" int vk_gemm_bf16(const VkGemmDesc* d_in, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int rc = validate(d_in);
+extern "C" int vk_gemm_bf16(const VkGemmDesc* d, void* stream) {
+    VkGemmDesc q;
+    GemmPlan p;
+    const int rc = plan_for(d, q, false, false, p);
     if (rc != VK_OK) return rc;
-    if (d_in->gnstat_out && vk_gemm_gnstat_fit(d_in) <= 0) return VK_EINVAL;   // (never a silent launch without the statistics the caller will read)
-    VkGemmDesc dq = *d_in;
-    norm_row_range(dq);   // m_end = M unless the caller asked for a row range (validate() checked it)
-    if (dq.m_begin == 0 && dq.m_end == dq.M && stream_fit(d_in)) return vk_gemm_stream_launch(&dq, stream_);
-    if ((dq.tile_cfg & 7) == 6) dq.tile_cfg &= ~7;   // streaming variant requested for a problem it does not take: the launcher's own choice
-    const VkGemmDesc* d = &dq;
-    const bool f32 = d->out_f32 != 0;
-    switch (d->epi) {
-        case EPI_LINEAR:
-            if ((d->ldc % 4) != 0) return VK_EINVAL;
-            if (d->amode == AMODE_DENSE) return f32 ? launch<AMODE_DENSE, EPI_LINEAR, true>(d, stream) : launch<AMODE_DENSE, EPI_LINEAR, false>(d, stream);
-            if (d->amode == AMODE_CONV3X3) return f32 ? launch<AMODE_CONV3X3, EPI_LINEAR, true>(d, stream) : launch<AMODE_CONV3X3, EPI_LINEAR, false>(d, stream);
-            if (d->amode == AMODE_TEMPORAL3) return f32 ? launch<AMODE_TEMPORAL3, EPI_LINEAR, true>(d, stream) : launch<AMODE_TEMPORAL3, EPI_LINEAR, false>(d, stream);
-            if (d->amode == AMODE_CONV3D) return f32 ? launch<AMODE_CONV3D, EPI_LINEAR, true>(d, stream) : launch<AMODE_CONV3D, EPI_LINEAR, false>(d, stream);
-            return VK_EINVAL;
-        case EPI_GEGLU:
-            if (d->amode != AMODE_DENSE || f32 || (d->N % 32) != 0) return VK_EINVAL;  // whole [16 value | 16 gate] fragments
-            return launch<AMODE_DENSE, EPI_GEGLU, false>(d, stream);
-        case EPI_TRANS:
-            if (d->amode != AMODE_DENSE || f32 || d->S <= 0 || (d->S % 4) != 0) return VK_EINVAL;
-            return launch<AMODE_DENSE, EPI_TRANS, false>(d, stream);
-    }
-    return VK_EINVAL;
+    if (q.gnstat_out && p.gnstat_slots <= 0) return VK_EINVAL;   // (never a silent launch without the statistics the caller will read)
+    return run_plan(&q, p, (hipStream_t)stream);
 }

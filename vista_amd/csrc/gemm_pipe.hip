@@ -17,64 +17,30 @@
 //   * LINEAR launches run one tile per workgroup (a workgroup that ends does not wait for its stores); GEGLU launches walk the tile list with
 //     256 resident workgroups and stage the next tile's first K-step before the epilogue.
 // Internal entry points, called by gemm.hip's launcher.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "common.h"
 #include "vista_hip.h"
 
 #include "gemm_common.h"
 
-#ifdef PIPE_W4   // the second compile of this file has entry points (and a kernel name in the profiles) of its own
-#define vk_gemm_pipe_fit vk_gemm_pipe4_fit
-#define vk_gemm_pipe_gnstat_ok vk_gemm_pipe4_gnstat_ok
-#define vk_gemm_pipe_launch vk_gemm_pipe4_launch
-#define gemm_pipe_kernel gemm_pipe4_kernel
-#endif
-
 namespace {
 
-// PIPE_W4 (gemm_pipe4.hip compiles this file a second time with it): the SAME kernel as FOUR waves of 128 x 160 -- one wave per SIMD, a 512-register
-// budget (320 accumulator registers, most of them AGPRs), 9 ds_read_b128 per 20 MFMAs instead of 7 per 10 and half the waves at every barrier; the
-// pieces are 32 rows (4 waves x 8 rows), 10 weight + 8 activation pieces per wave and K-step. Round-6 experiment: profiles/r06_gemm_pipe4.txt.
-#ifdef PIPE_W4
-constexpr int PBM = 256, PBN = 320, PNT = 256;
-constexpr int PFX = 5, PFY = 4;
-#else
+// (The same kernel as FOUR waves of 128 x 160, one per SIMD with a 512-register budget, was built in round 6 and measured 3-20 % behind:
+// profiles/r06_gemm_pipe4.txt.)
 constexpr int PBM = 256, PBN = 320, PNT = 512;
 constexpr int PFX = 5, PFY = 2;                // weight (MFMA row operand) / activation (column operand) fragments per wave
-#endif
 constexpr int PRPP = PNT / 8;                  // tile rows per piece (every wave moves 8 rows of a piece)
 constexpr int PAP = PBM / PRPP, PWP = PBN / PRPP;
 constexpr int PA_BYTES = PBM * 128, PSTAGE = (PBM + PBN) * 128;
-constexpr int PCAP = PNT == 512 ? 256 : 432;   // what the epilogue sizes its residual ring by: 16 registers per accumulator + the ring must fit the ARCH VGPRs (four-wave build: 256 of the 320 accumulator registers are AGPRs, so 432 - 320 - 36 = 76 registers of ring)
+constexpr int PCAP = 256;                      // what the epilogue sizes its residual ring by: 16 registers per accumulator + the ring must fit the VGPRs
 constexpr int APAR0 = 6 * PAP;                 // first bit of the CONV3X3 upsample parities in the validity word
-typedef std::conditional<(8 * PAP > 32), unsigned long long, unsigned>::type amask_t;
+typedef unsigned amask_t;                      // (8 * PAP = 32 validity + parity bits)
 constexpr unsigned P_OOB = 0xffffff00u;        // an offset no resource below reaches (host: every operand < P_LIMIT bytes)
 constexpr unsigned long long P_LIMIT = 0xfffff000ull;
-static_assert(PAP + PWP <= PFX * PFY && 8 * PAP <= 64, "the piece schedule issues one piece after each MFMA of the first k-substep");
+static_assert(PAP + PWP <= PFX * PFY && 8 * PAP <= 32, "the piece schedule issues one piece after each MFMA of the first k-substep");
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-// The MFMA of the K-loop. Eight-wave build: the builtin. Four-wave build: 320 accumulator registers do not fit the 256 AGPRs, and left to itself the register
-// allocator shuttles accumulators between the two halves of the file inside the loop (1060 v_accvgpr moves and 109 scratch accesses per K-step in the first
-// build) -- so the accumulators of weight fragments 0..3 are PINNED to AGPRs and those of fragment 4 to VGPRs by the operand constraints of an inline-asm MFMA.
-#ifdef PIPE_W4
-#if VK_F16
-#define PIPE_MFMA_OP "v_mfma_f32_32x32x16_f16"
-#else
-#define PIPE_MFMA_OP "v_mfma_f32_32x32x16_bf16"
-#endif
-template <bool AG>
-__device__ __forceinline__ void pipe_mfma(const bf16x8_t& x, const bf16x8_t& y, f32x16_t& c) {
-    if constexpr (AG) asm volatile(PIPE_MFMA_OP " %0, %1, %2, %0" : "+a"(c) : "v"(x), "v"(y));
-    else asm volatile(PIPE_MFMA_OP " %0, %1, %2, %0" : "+v"(c) : "v"(x), "v"(y));
-}
-#define PIPE_MMA(FI, X, Y, C) do { if ((FI) < 4) pipe_mfma<true>(X, Y, C); else pipe_mfma<false>(X, Y, C); } while (0)
-#else
 #define PIPE_MMA(FI, X, Y, C) C = vk_mfma(X, Y, C)
-#endif
 
 #define PIPE_SB() __builtin_amdgcn_sched_barrier(0)
 
@@ -89,7 +55,7 @@ __device__ __forceinline__ void pipe_mfma(const bf16x8_t& x, const bf16x8_t& y, 
 // XCD's L2, so that the LDS-DMA of the next iteration finds them there. It is the youngest vector-memory operation at the K-step barrier, whose wait
 // therefore becomes vmcnt(1) + a raw s_barrier (__syncthreads() would wait for it: vmcnt(0)). No arithmetic changes: results are bitwise the same.
 template <int AMODE, int EPI, bool NT_A, bool SPLIT, int GN_CPG = 0, int GN_NRES = 0, bool PF = false>
-__global__ __launch_bounds__(PNT, PNT == 512 ? 2 : 1) void gemm_pipe_kernel(const VkGemmDesc p, const int ksplit) {
+__global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, const int ksplit) {
     static_assert(!PF || AMODE == AMODE_DENSE, "the L2 prefetch is written for the dense loader");
     constexpr int LN_OFF = 2 * PSTAGE, EV_OFF = LN_OFF + PBM * 8;
     constexpr int NTAPS = (AMODE == AMODE_CONV3X3) ? 9 : (AMODE == AMODE_TEMPORAL3) ? 3 : 1;
@@ -135,7 +101,7 @@ __global__ __launch_bounds__(PNT, PNT == 512 ? 2 : 1) void gemm_pipe_kernel(cons
         // re-reads already hit -- the frame-fastest order measured 4 % SLOWER: profiles/r06_temporal_tile_order.txt), whole pixel blocks (S % 256 == 0), whole
         // row range; the arithmetic per tile is untouched: bitwise the same output.
         if constexpr (AMODE == AMODE_TEMPORAL3) {
-            if (p.tile_cfg & 8) return;   // (A/B: VISTA_T3_ORDER=0 keeps the row order)
+            if (p.tile_cfg & 8) return;   // (the row order of rounds 4 / 5; validate() admits no descriptor with the bit, the test stays so that the kernel's code does)
             const int nblk = p.S / PBM;
             if (nblk * PBM == p.S && p.m_begin == 0 && tilesM == (p.M / p.S) * nblk && (long long)p.S * p.Cin * 2 > (3LL << 20)) {
                 const int per_clip = p.T * nblk, clip = tm / per_clip, r = tm - clip * per_clip;
@@ -203,12 +169,6 @@ __global__ __launch_bounds__(PNT, PNT == 512 ? 2 : 1) void gemm_pipe_kernel(cons
         }
     };
 
-#ifdef PIPE_W4
-#ifndef PIPE_W4_SPREAD
-#define PIPE_W4_SPREAD 0
-#endif
-    constexpr bool w4_spread = PIPE_W4_SPREAD != 0;   // A/B at COMPILE time (-DPIPE_W4_SPREAD=1): two K-loop bodies behind a run-time flag spill 1.2-1.7 KB per lane
-#endif
     const int nk_all = p.K / BK;
     int nk = nk_all;        // K-steps of this workgroup (SPLIT: of its slice, set below)
     int tap = 0, c0b = 0;   // (tap, channel-slab byte offset) of the NEXT K-step to stage (conv loaders: K-step = (slab kt / NTAPS, tap kt % NTAPS))
@@ -299,25 +259,6 @@ __global__ __launch_bounds__(PNT, PNT == 512 ? 2 : 1) void gemm_pipe_kernel(cons
             }
     };
 
-#ifdef PIPE_W4
-    // four-wave build: with one wave per SIMD nothing runs in the shadow of a piece's issue stall, and eighteen pieces in a row cost more than eighteen
-    // spread out (MI355X_MICROARCH: 60 cycles among bare MFMAs, 100-185 inside a phase already carrying pieces) -> one piece after every SECOND MFMA of the
-    // first two k-substeps (q0 = 0 / PWP + PAP - 9 ...): pieces [q0, q0 + n) of the next K-step
-    auto mma_dma_spread = [&](const bf16x8_t* xf, const bf16x8_t* yf, const int stage, const int q0, const int n) __attribute__((always_inline)) {
-#pragma unroll
-        for (int fi = 0; fi < PFX; ++fi)
-#pragma unroll
-            for (int fj = 0; fj < PFY; ++fj) {
-                PIPE_MMA(fi, xf[fi], yf[fj], acc[fi][fj]);
-                const int u = fi * PFY + fj;
-                if ((u & 1) == 0 && (u >> 1) < n) {
-                    PIPE_SB();
-                    dma_q(q0 + (u >> 1), stage);
-                    PIPE_SB();
-                }
-            }
-    };
-#endif
 
     float2* const lnrow = (float2*)(smem + LN_OFF);
     float* const epi_vec = (float*)(smem + EV_OFF);
@@ -382,24 +323,6 @@ __global__ __launch_bounds__(PNT, PNT == 512 ? 2 : 1) void gemm_pipe_kernel(cons
         load_frags(st, 1, xb, yb);
         for (int kt = 0; kt + 1 < nk; ++kt) {
             PIPE_SB();
-#ifdef PIPE_W4
-            if constexpr (w4_spread) {
-                mma_dma_spread(xa, ya, st ^ 1, 0, 9);
-                PIPE_SB();
-                load_frags(st, 2, xa, ya);
-                PIPE_SB();
-                mma_dma_spread(xb, yb, st ^ 1, 9, PWP + PAP - 9);
-                dma_next();
-            } else {
-                mma_dma(xa, ya, st ^ 1);
-                dma_next();
-                PIPE_SB();
-                load_frags(st, 2, xa, ya);
-                PIPE_SB();
-                mma(xb, yb);
-            }
-            PIPE_SB();
-#else
             mma_dma(xa, ya, st ^ 1);
             dma_next();
             prefetch(kt + 2 < nk);   // (kb now names K-step kt + 2)
@@ -408,7 +331,6 @@ __global__ __launch_bounds__(PNT, PNT == 512 ? 2 : 1) void gemm_pipe_kernel(cons
             PIPE_SB();
             mma(xb, yb);
             PIPE_SB();
-#endif
             load_frags(st, 3, xb, yb);
             PIPE_SB();
             mma(xa, ya);
@@ -449,9 +371,6 @@ __global__ __launch_bounds__(PNT, PNT == 512 ? 2 : 1) void gemm_pipe_kernel(cons
         PIPE_SB();
         mma(xb, yb);
         PIPE_SB();
-#ifdef PIPE_W4   // the hazard recogniser does not see inside the inline-asm MFMAs: their results are read (v_accvgpr_read / VALU) only after the pipe has drained
-        asm volatile("s_nop 15\n s_nop 15" ::: "memory");
-#endif
 #ifdef PIPE_TIMING
         unsigned long long tm_t1;
         asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tm_t1) :: "memory");
@@ -520,16 +439,11 @@ template <int AMODE, int EPI>
 int pipe_launch(const VkGemmDesc* d, hipStream_t stream, int ksplit) {
     const int tilesN = d->N / PBN, tilesM = (d->m_end - d->m_begin + PBM - 1) / PBM;   // (the caller normalised the row range)
     const int ntiles = tilesM * tilesN;
-    VkGemmDesc desc = *d;
-    if constexpr (AMODE == AMODE_TEMPORAL3) {   // VISTA_T3_ORDER=0: the row tile order of rounds 4 / 5 instead of the frame-fastest one (A/B hook; kernel: tile_of)
-        static const bool rows = [] { const char* e = getenv("VISTA_T3_ORDER"); return e && atoi(e) == 0; }();
-        desc.tile_cfg = rows ? (desc.tile_cfg | 8) : (desc.tile_cfg & ~8);
-    }
     const bool nt_a = (AMODE == AMODE_DENSE && tilesN <= 4);   // as gemm.hip's launch_cfg: activation rows that few column tiles re-read are streamed non-temporally
     if constexpr (EPI == EPI_LINEAR) {
         if (ksplit > 1) {   // K slices x tiles; the caller (gemm.hip) runs the finishing pass
-            if (nt_a) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, AMODE == AMODE_DENSE, true>), dim3(ntiles * ksplit), dim3(PNT), 0, stream, desc, ksplit);
-            else hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, false, true>), dim3(ntiles * ksplit), dim3(PNT), 0, stream, desc, ksplit);
+            if (nt_a) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, AMODE == AMODE_DENSE, true>), dim3(ntiles * ksplit), dim3(PNT), 0, stream, *d, ksplit);
+            else hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, false, true>), dim3(ntiles * ksplit), dim3(PNT), 0, stream, *d, ksplit);
             VK_CHECK_LAUNCH();
             return VK_OK;
         }
@@ -539,15 +453,13 @@ int pipe_launch(const VkGemmDesc* d, hipStream_t stream, int ksplit) {
     // per tile -- a workgroup that ends does not wait for its stores, so the next one's first pieces fly while they drain, whereas the tile
     // walk's first barrier (vmcnt(0)) of the next tile waits for every store of the last: measured -7..-10 % on the short-K level-0 / level-1
     // shapes, +-1 % on the deep-K ones (same-box sweep, profiles/r04_gemm_pipe.txt)
-    // VISTA_GEGLU_WALK=0: one workgroup per GEGLU tile as well (A/B hook: do two concurrent half-batch launches interleave better than two tile walks?)
-    static const bool geglu_walk = [] { const char* e = getenv("VISTA_GEGLU_WALK"); return !e || atoi(e) != 0; }();
-    const int grid = (EPI == EPI_GEGLU && ntiles > 256 && geglu_walk) ? 256 : ntiles;
+    const int grid = (EPI == EPI_GEGLU && ntiles > 256) ? 256 : ntiles;
     if constexpr (EPI == EPI_LINEAR && AMODE != AMODE_DENSE) {
-        if (desc.gnstat_out) {   // (vk_gemm_pipe_launch checked vk_gemm_pipe_gnstat_ok: N = 320 / 640 / 1280, at most one residual tensor)
-            const int nres = (desc.res1 != nullptr) + (desc.res2 != nullptr);
-#define VK_PIPE_GN(CPG, NR) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, false, false, CPG, NR>), dim3(grid), dim3(PNT), 0, stream, desc, 1)
-            if (desc.N == 320) { if (nres == 0) VK_PIPE_GN(10, 0); else VK_PIPE_GN(10, 1); }
-            else if (desc.N == 640) { if (nres == 0) VK_PIPE_GN(20, 0); else VK_PIPE_GN(20, 1); }
+        if (d->gnstat_out) {   // (vk_gemm_pipe_launch checked vk_gemm_pipe_gnstat_ok: N = 320 / 640 / 1280, at most one residual tensor)
+            const int nres = (d->res1 != nullptr) + (d->res2 != nullptr);
+#define VK_PIPE_GN(CPG, NR) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, false, false, CPG, NR>), dim3(grid), dim3(PNT), 0, stream, *d, 1)
+            if (d->N == 320) { if (nres == 0) VK_PIPE_GN(10, 0); else VK_PIPE_GN(10, 1); }
+            else if (d->N == 640) { if (nres == 0) VK_PIPE_GN(20, 0); else VK_PIPE_GN(20, 1); }
             else { if (nres == 0) VK_PIPE_GN(40, 0); else VK_PIPE_GN(40, 1); }
 #undef VK_PIPE_GN
             VK_CHECK_LAUNCH();
@@ -559,18 +471,16 @@ int pipe_launch(const VkGemmDesc* d, hipStream_t stream, int ksplit) {
         // K-loop is long enough to have something to prefetch AND the launch is at most one round of tiles. Measured (profiles/r06_gemm_prefetch.txt): a
         // launch that fills the chip for several rounds is bound by request throughput, not latency, and the second request per line costs 2-5 % (step +1 ms
         // with the prefetch everywhere); an under-filled launch (the deep levels, every level of a frame-sharded rank) waits out the full memory latency in
-        // each K-step and gains 3-33 %. VISTA_GEMM_PF: unset = this rule, 1 = every dense launch, 0 = never (A/B hooks; bitwise the same results).
-        static const int pf_env = [] { const char* e = getenv("VISTA_GEMM_PF"); return e ? atoi(e) : -1; }();
-        const bool pf_want = PNT == 512 && (pf_env < 0 ? ntiles <= 256 : pf_env != 0);   // (the prefetch's lane -> row map is written for 512 threads)
-        if (pf_want && d->K >= 3 * BK && (d->lda % 64) == 0 && (((size_t)d->A) & 127) == 0) {
-            if (nt_a) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, true, false, 0, 0, true>), dim3(grid), dim3(PNT), 0, stream, desc, 1);
-            else hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, false, false, 0, 0, true>), dim3(grid), dim3(PNT), 0, stream, desc, 1);
+        // each K-step and gains 3-33 %. Bitwise the same results either way.
+        if (ntiles <= 256 && d->K >= 3 * BK && (d->lda % 64) == 0 && (((size_t)d->A) & 127) == 0) {
+            if (nt_a) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, true, false, 0, 0, true>), dim3(grid), dim3(PNT), 0, stream, *d, 1);
+            else hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, false, false, 0, 0, true>), dim3(grid), dim3(PNT), 0, stream, *d, 1);
             VK_CHECK_LAUNCH();
             return VK_OK;
         }
     }
-    if (nt_a) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, AMODE == AMODE_DENSE, false>), dim3(grid), dim3(PNT), 0, stream, desc, 1);
-    else hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, false, false>), dim3(grid), dim3(PNT), 0, stream, desc, 1);
+    if (nt_a) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, AMODE == AMODE_DENSE, false>), dim3(grid), dim3(PNT), 0, stream, *d, 1);
+    else hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, false, false>), dim3(grid), dim3(PNT), 0, stream, *d, 1);
     VK_CHECK_LAUNCH();
     return VK_OK;
 }
@@ -615,13 +525,8 @@ extern "C" int vk_gemm_pipe_launch(const VkGemmDesc* d, void* stream_, int kspli
     if (!vk_gemm_pipe_fit(d)) return VK_EINVAL;
     if (ksplit > 1 && (d->epi != EPI_LINEAR || !d->splitk_ws || d->ln_stats || d->rowstat_out || d->act)) return VK_EINVAL;
     if (d->gnstat_out && !vk_gemm_pipe_gnstat_ok(d, ksplit)) return VK_EINVAL;
-#ifndef VK_PIPE_ONLY   // (-DVK_PIPE_ONLY=<amode>: a one-loader build for tuning sessions)
-#define VK_PIPE_ONLY -1
-#endif
-    constexpr int only = VK_PIPE_ONLY;
-    if constexpr (only < 0 || only == AMODE_DENSE) if (d->amode == AMODE_DENSE)
-        return d->epi == EPI_GEGLU ? pipe_launch<AMODE_DENSE, EPI_GEGLU>(d, stream, ksplit) : pipe_launch<AMODE_DENSE, EPI_LINEAR>(d, stream, ksplit);
-    if constexpr (only < 0 || only == AMODE_CONV3X3) if (d->amode == AMODE_CONV3X3) return pipe_launch<AMODE_CONV3X3, EPI_LINEAR>(d, stream, ksplit);
-    if constexpr (only < 0 || only == AMODE_TEMPORAL3) if (d->amode == AMODE_TEMPORAL3) return pipe_launch<AMODE_TEMPORAL3, EPI_LINEAR>(d, stream, ksplit);
+    if (d->amode == AMODE_DENSE) return d->epi == EPI_GEGLU ? pipe_launch<AMODE_DENSE, EPI_GEGLU>(d, stream, ksplit) : pipe_launch<AMODE_DENSE, EPI_LINEAR>(d, stream, ksplit);
+    if (d->amode == AMODE_CONV3X3) return pipe_launch<AMODE_CONV3X3, EPI_LINEAR>(d, stream, ksplit);
+    if (d->amode == AMODE_TEMPORAL3) return pipe_launch<AMODE_TEMPORAL3, EPI_LINEAR>(d, stream, ksplit);
     return VK_EINVAL;
 }

@@ -541,12 +541,11 @@ int gn_stats(const void* x, const void* x2, int C1, float* sums, float* partial_
     return gn_finalize(partial_ws, sums, g.ngroups, frames_per_group * g.nchunks, stream);
 }
 
-// Slots per image group of the statistics pass when the apply pass may fold them itself (0 = keep the finalize launch): at most GN_FOLD_MAX,
-// VISTA_GN_FOLD=0 restores the three-launch GroupNorm everywhere (A/B hook; bitwise the same output either way).
+// Slots per image group of the statistics pass when the apply pass may fold them itself (0 = keep the finalize launch): at most GN_FOLD_MAX
+// (bitwise the same output either way).
 int gn_fold_parts(int32_t n_img, int32_t S, int32_t C, int32_t frames_per_group) {
-    static const bool on = [] { const char* e = getenv("VISTA_GN_FOLD"); return !e || atoi(e) != 0; }();
     GnGeom g;
-    if (!on || !gn_geom(n_img, S, C, frames_per_group, g)) return 0;
+    if (!gn_geom(n_img, S, C, frames_per_group, g)) return 0;
     const long long np = (long long)frames_per_group * g.nchunks;
     return np <= GN_FOLD_MAX ? (int)np : 0;
 }
@@ -602,10 +601,7 @@ extern "C" int vk_groupnorm_apply_bf16(const void* x, void* y, const float* gamm
 // ABI v7: the apply pass on STAGE-1 slots (a GEMM epilogue's VkGemmDesc.gnstat_out, one slot per 64 output rows: nchunks = S / 64 per image), folding
 // them itself -- two launches per GroupNorm (producer, apply) instead of three. Needs frames_per_group * nchunks <= vk_groupnorm_fold_max() (else
 // VK_EINVAL: run vk_groupnorm_finalize_partials + vk_groupnorm_apply_bf16). Bitwise the output of that pair.
-extern "C" int vk_groupnorm_fold_max(void) {
-    static const bool on = [] { const char* e = getenv("VISTA_GN_FOLD"); return !e || atoi(e) != 0; }();
-    return on ? GN_FOLD_MAX : 0;
-}
+extern "C" int vk_groupnorm_fold_max(void) { return GN_FOLD_MAX; }
 
 extern "C" int vk_groupnorm_apply_partials_bf16(const void* x, void* y, const float* gamma, const float* beta, const float* partial, int32_t n_img,
                                                 int32_t S, int32_t C, int32_t nchunks, int32_t frames_per_group, float count, float eps, int32_t silu,

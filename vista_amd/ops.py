@@ -333,17 +333,25 @@ class GnPartials:
         self.t, self.nchunks, self.rows, self.C = None, 0, 0, 0
 
 
+def _prepare(desc):
+    """What every vk_gemm_* call about `desc`, query or launch, must see alike: the forced tile variant, the row range and the split-K workspace
+    (the launcher's decisions read all three). Returns the stream."""
+    desc.tile_cfg = TILE_CFG
+    if ROW_RANGE is not None:
+        desc.m_begin, desc.m_end = ROW_RANGE
+    stream = _stream()
+    if SPLITK_WS_BYTES:
+        ws = _splitk_workspace(stream)
+        desc.splitk_ws, desc.splitk_ws_bytes = _p(ws), ws.numel() * 4
+    return stream
+
+
 def _ask_gn(d, gn, rows_per_image, device):
     """Before the launch: if this GEMM can emit the GroupNorm statistics of its output, give it the buffer."""
-    if gn is None or not GN_EPI:
+    if gn is None or not GN_EPI or ROW_RANGE is not None:   # (a row-range launch never emits)
         return
     d.gn_rows = int(rows_per_image)
-    d.tile_cfg = TILE_CFG
-    if ROW_RANGE is not None:
-        return
-    if SPLITK_WS_BYTES:   # (the launcher's split-K decision looks at the workspace: ask with what _gemm will set)
-        ws = _splitk_workspace(_stream())
-        d.splitk_ws, d.splitk_ws_bytes = _p(ws), ws.numel() * 4
+    _prepare(d)
     slots = _lib.load().vk_gemm_gnstat_fit(C.byref(d))
     if slots < 0:
         raise _lib.VistaHipError(f"vk_gemm_gnstat_fit failed with code {slots}")
@@ -353,16 +361,9 @@ def _ask_gn(d, gn, rows_per_image, device):
         d.gnstat_out = _p(gn.t)
 
 
-
 def _gemm(desc, emit_stats=False, device=None):
     lib = _lib.load()
-    desc.tile_cfg = TILE_CFG
-    if ROW_RANGE is not None:
-        desc.m_begin, desc.m_end = ROW_RANGE
-    stream = _stream()
-    if SPLITK_WS_BYTES:
-        ws = _splitk_workspace(stream)
-        desc.splitk_ws, desc.splitk_ws_bytes = _p(ws), ws.numel() * 4
+    stream = _prepare(desc)
     stats = None
     if emit_stats:
         parts = lib.vk_gemm_rowstat_parts(C.byref(desc))
