@@ -365,6 +365,29 @@ int vk_gaussian_sample(const float* moments, const float* noise, float* out, int
  * latents, reduced in a fixed order (f64 partials; partial_ws: 512 doubles). The caller forms exp(-out/n). */
 int vk_ensemble_variance_sum(const float* x, double* out, double* partial_ws, int32_t E, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------ image I/O of the sampling front door (ABI v8; csrc/image_io.hip)
+ * Storage-type independent: the same code is linked into both libraries.
+ *
+ * vk_lanczos_resize_u8: `load_img` (sample.py:174-201) for n_img frames of one size -- crop box, PIL `resize(LANCZOS)`, ToTensor, x * 2 - 1.
+ *   src   (n_img, src_h, src_w, 3) uint8 RGB, interleaved; the crop box [top, top + crop_h) x [left, left + crop_w) is read in place
+ *   tmp   (n_img, crop_h, out_w, 3) uint8 scratch of the caller: the horizontal pass's 8-bit intermediate, as in Pillow (4-byte aligned)
+ *   out   (n_img, 3, out_h, out_w) fp32 (16-byte aligned): lut256[byte], lut256[k] = float(k) / 255 * 2 - 1 as the caller computed it in IEEE fp32
+ *   bounds_x (out_w, 2) int32 = (first tap's column inside the crop box, tap count <= ksize_x); coef_x (out_w, ksize_x) int32 fixed-point weights
+ *   (2^22 scale); bounds_y / coef_y / ksize_y the same for the rows. The tables are Pillow's `precompute_coeffs` + `normalize_coeffs_8bpc`
+ *   (vista_amd/image_io.py: lanczos_tables); a value is clip8((2^21 + sum pixel * weight) >> 22) per pass, in int32 -- every byte equals Pillow's.
+ *   The caller guarantees 0 <= first + count <= crop_w (crop_h); the entry point checks the box against the source and returns VK_EINVAL for an
+ *   empty or overhanging one. */
+int vk_lanczos_resize_u8(const void* src, void* tmp, float* out, const int32_t* bounds_x, const int32_t* coef_x, int32_t ksize_x,
+                         const int32_t* bounds_y, const int32_t* coef_y, int32_t ksize_y, const float* lut256, int32_t n_img,
+                         int32_t src_h, int32_t src_w, int32_t left, int32_t top, int32_t crop_h, int32_t crop_w, int32_t out_h,
+                         int32_t out_w, void* stream);
+/* vk_frames_to_u8: the float -> uint8 conversion of `perform_save_locally` (sample_utils.py:96-137). x (n_img, 3, H, W) fp32 (16-byte aligned).
+ *   real = 0: uint8(255 * x)   real = 1: uint8(255 * (x + 1) / 2)   -- numpy's float32 arithmetic (one rounding per operation), truncating cast.
+ *   pad = 0: out (n_img, H, W, 3) uint8.   pad > 0: out is ONE (ymaps * (H + pad) + pad, xmaps * (W + pad) + pad, 3) canvas, ymaps =
+ *   ceil(n_img / xmaps), tile k at row k / xmaps * (H + pad) + pad, column k % xmaps * (W + pad) + pad; every other pixel is the map of 0
+ *   (torchvision.utils.make_grid with pad_value 0, written straight from the NCHW tensor). out 4-byte aligned. */
+int vk_frames_to_u8(const float* x, void* out, int32_t n_img, int32_t H, int32_t W, int32_t xmaps, int32_t pad, int32_t real, void* stream);
+
 /* library info */
 int vk_abi_version(void);
 /* ABI v7: the 16-bit storage type this library was built for: 0 = bf16 (libvista_hip.so, the default and the BASELINE config's dtype), 1 = IEEE fp16

@@ -57,7 +57,7 @@ class VkGemmDesc(C.Structure):
     ]
 
 
-ABI_VERSION = 7  # vk_abi_version() of the library this table mirrors
+ABI_VERSION = 8  # vk_abi_version() of the library this table mirrors
 
 # name -> argtypes; every entry returns int. Must list every symbol include/vista_hip.h declares
 # (tests/test_abi.py checks the header against this table and against the built library).
@@ -109,6 +109,8 @@ SIGNATURES = {
     "vk_scale_rows": [_vp, _vp, _vp, _i32, _i32, _vp],
     "vk_gaussian_sample": [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp],
     "vk_ensemble_variance_sum": [_vp, _vp, _vp, _i32, _i64, _vp],
+    "vk_lanczos_resize_u8": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "vk_frames_to_u8": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "vk_abi_version": [],
     "vk_act_dtype": [],
 }

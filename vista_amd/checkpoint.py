@@ -5,7 +5,7 @@
                                        the frozen projections (:10-31), strip the `_forward_module.` prefix (:33-36), replace
                                        weights by their EMA copies (:38-47)
 * `split_by_component(sd)`           - `model.diffusion_model.*` -> VideoUNet keys, `first_stage_model.decoder.*` -> VideoDecoder keys
-* `load_into(...)`                   - `load_state_dict(strict=False)` + the reference's missing / unexpected report (sample_utils.py:73-77)
+* `load_into(...)`                   - per component `load_state_dict(strict=False)` + the reference's missing / unexpected report (sample_utils.py:73-77)
 
 Tensors stay torch CPU tensors here; the bf16 packing for the HIP GEMMs happens lazily in each module (`Packable.packed()`),
 which `load_state_dict` invalidates.
@@ -14,6 +14,8 @@ import torch
 
 UNET_PREFIX = "model.diffusion_model."
 DECODER_PREFIX = "first_stage_model.decoder."
+ENCODER_PREFIX = "first_stage_model.encoder."
+CONDITIONER_PREFIX = "conditioner."
 _LORA = (("q_adapter_down", "q_adapter_up", "to_q"), ("k_adapter_down", "k_adapter_up", "to_k"), ("v_adapter_down", "v_adapter_up", "to_v"))
 
 
@@ -80,13 +82,16 @@ def split_by_component(sd):
     return parts
 
 
-def load_into(sd, unet=None, decoder=None, verbose=True):
-    """Loads the matching slices of a full Vista state dict into a vista_amd VideoUNet / VideoDecoder, `strict=False` like the
-    reference, and returns {"unet": (missing, unexpected), "decoder": (...)} -- names drifting silently is how one gets
+def load_into(sd, unet=None, decoder=None, verbose=True, encoder=None, conditioner=None):
+    """Loads the matching slices of a full Vista state dict into a vista_amd VideoUNet / VideoDecoder and -- optionally -- the first-stage
+    Encoder (`first_stage_model.encoder.*`) and the GeneralConditioner (`conditioner.*`), `strict=False` like the reference, and returns
+    {"unet": (missing, unexpected), "decoder": (...), ...} for the modules given -- names drifting silently is how one gets
     "a sequence of blur" (docs/SAMPLING.md:33), so callers should assert both lists are empty."""
     parts = split_by_component(sd)
+    for name, prefix in (("encoder", ENCODER_PREFIX), ("conditioner", CONDITIONER_PREFIX)):
+        parts[name] = {k[len(prefix):]: v for k, v in parts["rest"].items() if k.startswith(prefix)}
     report = {}
-    for name, mod in (("unet", unet), ("decoder", decoder)):
+    for name, mod in (("unet", unet), ("decoder", decoder), ("encoder", encoder), ("conditioner", conditioner)):
         if mod is None:
             continue
         res = mod.load_state_dict(parts[name], strict=False)

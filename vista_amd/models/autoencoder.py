@@ -26,9 +26,17 @@ class DiagonalGaussianRegularizer(nn.Module):
 
 
 class AutoencodingEngine(nn.Module):
-    def __init__(self, encoder=None, decoder=None, regularizer=None):
+    """Built from module objects (encoder=, decoder=, regularizer=) or, like the reference's class, from config entries
+    (configs/inference/vista.yaml:146-184: encoder_config / decoder_config / regularizer_config; loss_config and the training options are
+    accepted and unused)."""
+
+    def __init__(self, encoder=None, decoder=None, regularizer=None, *, encoder_config=None, decoder_config=None, regularizer_config=None,
+                 loss_config=None, **ignored):
         super().__init__()
-        self.encoder, self.decoder = encoder, decoder
+        from ..util import instantiate_from_config
+        build = lambda obj, cfg: obj if obj is not None or cfg is None else instantiate_from_config(cfg)  # noqa: E731
+        self.encoder, self.decoder = build(encoder, encoder_config), build(decoder, decoder_config)
+        regularizer = build(regularizer, regularizer_config)
         self.regularization = regularizer if regularizer is not None else DiagonalGaussianRegularizer()
 
     def encode(self, x, return_reg_log=False, unregularized=False, scale=1.0):

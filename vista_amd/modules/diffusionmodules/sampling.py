@@ -70,6 +70,10 @@ class EulerEDMSampler(SingleStepDiffusionSampler):
         # the churn noise source, `x -> standard normal tensor like x` (reference: torch.randn_like, sampling.py:81). A hook so that a caller
         # -- like do_sample's noise_fn -- can inject its own draws (tests replay the draws recorded from the reference).
         self.noise_fn = None
+        # how the fused path runs the UNet of a step: replay of a captured hipGraph (`graph`) and the two guidance halves as two concurrent
+        # forwards (`cfg_streams`); see FusedLoop. None = the environment decides (VISTA_HIPGRAPH / VISTA_CFG_STREAMS, both off by default).
+        self.graph = None
+        self.cfg_streams = None
 
     # ---- generic path -------------------------------------------------------------------------------------------
     def sampler_step(self, sigma, next_sigma, denoiser, x, cond, cond_mask=None, uc=None, gamma=0.0):
@@ -124,7 +128,8 @@ class EulerEDMSampler(SingleStepDiffusionSampler):
     def _sample_fused(self, fd, x, cond, uc, cond_frame, maskf, replace, sig):
         """`self.shard` (a vista_amd.parallel.FrameShard, set by the caller on every rank) turns on frame sharding: every
         rank passes the same full-window tensors, works on its own frames and returns the gathered full result."""
-        loop = FusedLoop(self, fd, x.float().clone(), cond, uc, cond_frame, maskf, replace, sig, shard=getattr(self, "shard", None))
+        loop = FusedLoop(self, fd, x.float().clone(), cond, uc, cond_frame, maskf, replace, sig, shard=getattr(self, "shard", None),
+                         graph=self.graph, cfg_streams=self.cfg_streams)
         for i in range(len(sig) - 1):
             loop.step(i)
         return loop.finish().to(x.dtype)

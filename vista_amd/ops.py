@@ -1212,3 +1212,69 @@ def scale_rows(x, s):
     n = x.shape[0]
     check(_lib.load().vk_scale_rows(_p(x), _p(s), _p(out), n, x.numel() // n, _stream()), "vk_scale_rows")
     return out
+
+
+# ---- image I/O of the sampling front door (csrc/image_io.hip, ABI v8) ----
+_IMAGE_TABLES = {}   # (device, crop_w, crop_h, width, height) -> device copies of the Lanczos tables; "lut": the 256 output values
+
+
+def _image_tables(device, crop_w, crop_h, width, height):
+    from . import image_io
+    key = (str(device), crop_w, crop_h, width, height)
+    t = _IMAGE_TABLES.get(key)
+    if t is None:
+        bx, cx, kx = image_io.lanczos_tables(crop_w, width)
+        by, cy, ky = image_io.lanczos_tables(crop_h, height)
+        up = lambda a: torch.from_numpy(a.copy()).to(device)  # noqa: E731
+        if len(_IMAGE_TABLES) >= 16:
+            _IMAGE_TABLES.clear()
+        t = _IMAGE_TABLES[key] = (up(bx), up(cx), kx, up(by), up(cy), ky, up(image_io.unit_range_table()))
+    return t
+
+
+def load_img_batch(frames_u8, height, width, box=None):
+    """`load_img` (sample.py:174-201) for a stack of decoded frames: frames_u8 (n, h, w, 3) uint8 RGB on the GPU -> (n, 3, height, width) fp32 in
+    [-1, 1]. The centre crop (image_io.crop_box, or `box` = (left, top, crop_w, crop_h)) is applied through source offsets; the resize is Pillow's
+    8-bit LANCZOS, byte for byte (vk_lanczos_resize_u8), and the output values are ToTensor's k/255 followed by x * 2.0 - 1.0, bit for bit."""
+    from . import image_io
+    _need(frames_u8, torch.uint8, "frames_u8")
+    if frames_u8.dim() == 3:
+        frames_u8 = frames_u8[None]
+    if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise ValueError(f"load_img_batch: expected (n, h, w, 3) uint8 RGB frames, got {tuple(frames_u8.shape)}")
+    frames_u8 = frames_u8.contiguous()
+    n, sh, sw, _ = frames_u8.shape
+    left, top, cw, ch = image_io.crop_box(sw, sh, height, width) if box is None else box
+    dev = frames_u8.device
+    if cw <= 0 or ch <= 0:   # (the tables of an empty box do not exist: the entry point is asked all the same, and answers VK_EINVAL)
+        bx = cx = by = cy = lut = torch.zeros(4, dtype=torch.int32, device=dev)
+        kx = ky = 1
+    else:
+        bx, cx, kx, by, cy, ky, lut = _image_tables(dev, cw, ch, width, height)
+    tmp = torch.empty((n, max(ch, 1), width, 3), dtype=torch.uint8, device=dev)
+    out = torch.empty((n, 3, height, width), dtype=F32, device=dev)
+    check(_lib.load().vk_lanczos_resize_u8(_p(frames_u8), _p(tmp), _p(out), _p(bx), _p(cx), kx, _p(by), _p(cy), ky, _p(lut), n, sh, sw,
+                                           left, top, ch, cw, height, width, _stream()), "vk_lanczos_resize_u8")
+    return out
+
+
+def frames_to_u8(x, real=False, grid=False):
+    """The float -> uint8 conversion of `perform_save_locally` (sample_utils.py:96-137) on the GPU: x (n, 3, H, W) fp32 -> (n, H, W, 3) uint8, or
+    with grid=True ONE (rows, cols, 3) uint8 canvas laid out like torchvision.utils.make_grid(x, nrow=int(n ** 0.5)) (padding 2, pad value 0;
+    image_io.grid_geometry). real=False: uint8(255 * x) for samples in [0, 1]; real=True: uint8(255 * (x + 1) / 2) for inputs in [-1, 1] -- numpy's
+    float32 arithmetic and truncating cast, bit for bit. torchvision is not installed where this package is tested: the layout follows make_grid's
+    published source (a single image comes back without a border), parity with a live make_grid is not pinned by a test."""
+    from . import image_io
+    _need(x, F32, "x")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"frames_to_u8: expected (n, 3, H, W) fp32 frames, got {tuple(x.shape)}")
+    x = x.contiguous()
+    n, _, H, W = x.shape
+    if grid:
+        xmaps, _, rows, cols, pad = image_io.grid_geometry(n, H, W)
+        out = torch.empty((rows, cols, 3) if pad else (H, W, 3), dtype=torch.uint8, device=x.device)
+    else:
+        xmaps, pad = 1, 0
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=x.device)
+    check(_lib.load().vk_frames_to_u8(_p(x), _p(out), n, H, W, xmaps, pad, 1 if real else 0, _stream()), "vk_frames_to_u8")
+    return out

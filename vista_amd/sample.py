@@ -1,0 +1,171 @@
+"""`python -m vista_amd.sample`: pictures in, frames out -- the reference's sample.py on the MI355X.
+
+Every flag of the reference (sample.py:29-119) under its name with its default; on top: --config / --ckpt (one config, one checkpoint),
+--data_root / --anno_file (where the dataset lives) and --eager. On one GPU the sampler replays the UNet of a step from a captured hipGraph, the
+two guidance halves concurrently (sampler.graph = sampler.cfg_streams = True: the form bench.py measures, bitwise the eager result); --eager
+launches every kernel of every step from the host instead.
+
+    python -m vista_amd.sample --ckpt ckpts/vista.safetensors --dataset IMG --data_root image_folder --save outputs
+
+`run(...)` is the loop body as a function (returns the tensors instead of writing files), `main(argv)` the loop of sample.py:204-274.
+"""
+import argparse
+import os
+import random
+import sys
+import time
+
+import torch
+
+from . import config
+from . import sample_utils as SU
+
+UC_KEYS = ["cond_frames", "cond_frames_without_noise", "command", "trajectory", "speed", "angle", "goal"]
+
+
+def parse_args(**parser_kwargs):
+    parser = argparse.ArgumentParser(**parser_kwargs)
+    add = parser.add_argument
+    add("--version", type=str, default="vwm", help="model version")
+    add("--dataset", type=str, default="NUSCENES", help="dataset name")
+    add("--save", type=str, default="outputs", help="directory to save samples")
+    add("--action", type=str, default="free", help="action mode for control, such as traj, cmd, steer, goal")
+    add("--n_rounds", type=int, default=1, help="number of sampling rounds")
+    add("--n_frames", type=int, default=25, help="number of frames for each round")
+    add("--n_conds", type=int, default=1, help="number of initial condition frames for the first round")
+    add("--seed", type=int, default=23, help="random seed for seed_everything")
+    add("--height", type=int, default=576, help="target height of the generated video")
+    add("--width", type=int, default=1024, help="target width of the generated video")
+    add("--cfg_scale", type=float, default=2.5, help="scale of the classifier-free guidance")
+    add("--cond_aug", type=float, default=0.0, help="strength of the noise augmentation")
+    add("--n_steps", type=int, default=50, help="number of sampling steps")
+    add("--rand_gen", action="store_false", help="whether to generate samples randomly or sequentially")
+    add("--low_vram", action="store_true", help="accepted for compatibility; a no-op here (every stage stays resident in HBM)")
+    # not in the reference
+    add("--config", type=str, default=None, help="model config (default: the shipped configs/inference/vista_mi355x.yaml)")
+    add("--ckpt", type=str, default=None, help="checkpoint (default: ckpts/vista.safetensors)")
+    add("--data_root", type=str, default=None, help="dataset root (default: the reference's, data/nuscenes or image_folder)")
+    add("--anno_file", type=str, default=None, help="annotation JSON of the NUSCENES dataset (default: annos/nuScenes_val.json)")
+    add("--eager", action="store_true", help="launch every step's kernels from the host instead of replaying captured graphs")
+    return parser
+
+
+def seed_everything(seed):
+    """What pytorch_lightning.seed_everything seeds: Python's, numpy's and torch's generators (CPU and every GPU)."""
+    import numpy as np
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(seed)
+
+
+class _StageClock:
+    """Adds the wall time of the pipeline's condition / encode / decode calls to `timings` while it is active (a device sync on either side of
+    each call: a handful per run)."""
+    STAGES = (("condition_fn", "condition"), ("encode_first_stage", "encode"), ("decode_first_stage", "decode"))
+
+    def __init__(self, model, timings):
+        self.model, self.timings = model, timings
+
+    def _wrap(self, fn, stage):
+        def timed(*a, **k):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a, **k)
+            torch.cuda.synchronize()
+            self.timings[stage] = self.timings.get(stage, 0.0) + time.perf_counter() - t0
+            return out
+        return timed
+
+    def __enter__(self):
+        self.saved = {}
+        for attr, stage in self.STAGES:
+            self.saved[attr] = self.model.__dict__.get(attr)
+            setattr(self.model, attr, self._wrap(getattr(self.model, attr), stage))
+
+    def __exit__(self, *exc):
+        for attr, old in self.saved.items():
+            if old is None:
+                delattr(self.model, attr)
+            else:
+                setattr(self.model, attr, old)
+        return False
+
+
+def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames=25, n_rounds=1, n_conds=1, n_steps=50, cfg_scale=2.5,
+        cond_aug=0.0, eager=False, timings=None):
+    """One sample of the reference's loop (sample.py:222-254) without the files -> (samples in [0, 1], samples_z, inputs in [-1, 1]): load and
+    resize the frames, build the value dict, pick the guider (TrianglePredictionGuider for a rollout, VanillaCFG for one round), do_sample.
+    The caller seeds. `timings` (a dict) receives the wall time in seconds of load, condition, encode, decode and sample (= the rest of do_sample:
+    the denoising loops)."""
+    t0 = time.perf_counter()
+    images = SU.load_img_seq(frame_list, height, width, "cuda")
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    unique_keys = set(e.input_key for e in model.conditioner.embedders)
+    value_dict = SU.init_embedder_options(unique_keys)
+    cond_img = images[:1]
+    value_dict["cond_frames_without_noise"] = cond_img
+    value_dict["cond_aug"] = cond_aug
+    value_dict["cond_frames"] = cond_img + cond_aug * torch.randn_like(cond_img)
+    for key, value in (action_dict or {}).items():
+        value_dict[key] = value
+    sampler = SU.init_sampling(guider="TrianglePredictionGuider" if n_rounds > 1 else "VanillaCFG", steps=n_steps, cfg_scale=cfg_scale,
+                               num_frames=n_frames)
+    sampler.graph = sampler.cfg_streams = not eager   # (one GPU, no frame shard)
+    import contextlib
+    stages = {}
+    with (_StageClock(model, stages) if timings is not None else contextlib.nullcontext()):
+        out = SU.do_sample(images, model, sampler, value_dict, num_rounds=n_rounds, num_frames=n_frames, force_uc_zero_embeddings=UC_KEYS,
+                           initial_cond_indices=list(range(n_conds)))
+        torch.cuda.synchronize()
+    if timings is not None:
+        timings["load"] = t1 - t0
+        timings.update(stages)
+        timings["sample"] = time.perf_counter() - t1 - sum(stages.values())
+    return out
+
+
+def main(argv=None):
+    opt, _unknown = parse_args(prog="python -m vista_amd.sample").parse_known_args(argv)
+    # sizes the kernels cannot take are refused here, before 2.5 billion parameters are built
+    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
+    SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, net_params)
+    if opt.low_vram:
+        print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
+    spec = dict(SU.VERSION2SPECS[opt.version])
+    if opt.config:
+        spec["config"] = opt.config
+    if opt.ckpt:
+        spec["ckpt"] = opt.ckpt
+    model = SU.init_model(spec)
+    virtual_path, real_path = os.path.join(opt.save, "virtual"), os.path.join(opt.save, "real")
+
+    sample_index = 0
+    while sample_index >= 0:
+        seed_everything(opt.seed)
+        frame_list, sample_index, dataset_length, action_dict = SU.get_sample(sample_index, opt.dataset, opt.n_frames, opt.action,
+                                                                              data_root=opt.data_root, anno_file=opt.anno_file)
+        timings = {}
+        samples, samples_z, inputs = run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames,
+                                         n_rounds=opt.n_rounds, n_conds=opt.n_conds, n_steps=opt.n_steps, cfg_scale=opt.cfg_scale,
+                                         cond_aug=opt.cond_aug, eager=opt.eager, timings=timings)
+        t0 = time.perf_counter()
+        for path, frames in ((virtual_path, samples), (real_path, inputs)):
+            for mode in ("videos", "grids", "images"):
+                SU.perform_save_locally(path, frames, mode, opt.dataset, sample_index)
+        timings["save"] = time.perf_counter() - t0
+        print(f"sample {sample_index}: " + ", ".join(f"{k} {v:.2f} s" for k, v in timings.items()), flush=True)
+
+        if opt.rand_gen:
+            sample_index += random.randint(1, max(1, dataset_length - 1))
+        else:
+            sample_index += 1
+            if dataset_length <= sample_index:
+                sample_index = -1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
