@@ -388,6 +388,36 @@ int vk_lanczos_resize_u8(const void* src, void* tmp, float* out, const int32_t* 
  *   (torchvision.utils.make_grid with pad_value 0, written straight from the NCHW tensor). out 4-byte aligned. */
 int vk_frames_to_u8(const float* x, void* out, int32_t n_img, int32_t H, int32_t W, int32_t xmaps, int32_t pad, int32_t real, void* stream);
 
+/* ------------------------------------------------------------------ exchange packing of the frame-sharded step (ABI v9; csrc/reshard.hip)
+ * Storage-type independent: the same code is linked into both libraries.
+ *
+ * vk_copy_row_boxes: every row gather / scatter around an all-to-all of vista_amd/parallel.py (frames <-> pixels re-shards and their chunked
+ * form, the halo frames of the temporal convolutions, a rank's rows of a replicated tensor) as ONE launch. `src` is (src_rows, row_bytes) and
+ * `dst` (dst_rows, row_bytes), both dense and 16-byte aligned; row_bytes > 0 and a multiple of 16. A plan is 1 .. VK_RESHARD_MAX_BOXES boxes;
+ * box rows (b, t, s), 0 <= b < nb, 0 <= t < nt, 0 <= s < ns, are copied
+ *     src row  src_row + b * src_stride_b + t * src_stride_t + s   ->   dst row  dst_row + b * dst_stride_b + t * dst_stride_t + s
+ * (strides in rows, any sign), so the ns rows of one (b, t) are contiguous on both sides. `reserved` fields are ignored.
+ *   Plan passing: `boxes` is HOST memory, read during the call; the plan reaches the kernel by value in its argument. The entry point
+ *   allocates nothing, copies nothing and synchronises nothing: the caller may free or overwrite the plan as soon as the call returns, and the
+ *   launch may be captured into a graph and replayed.
+ *   Validation (VK_EINVAL before any launch, dst untouched): a null or misaligned pointer, row_bytes <= 0 or not a multiple of 16, n outside
+ *   [1, VK_RESHARD_MAX_BOXES], a negative extent or row count, a non-empty box that leaves [0, src_rows) on the source or [0, dst_rows) on
+ *   the destination (checked on the host in int64).
+ *   A box with a zero extent is legal and skipped; a plan of empty boxes only returns VK_OK without a launch.
+ *   Overlap: the caller guarantees that the destination rows of the boxes of one plan are pairwise distinct and that dst does not alias the
+ *   source rows read; source boxes may overlap (a stride of 0 repeats rows). Overlapping destinations are a data race: undefined contents. */
+#define VK_RESHARD_MAX_BOXES 32            /* T <= 32 frames bounds the ranks of a frame-shard group */
+typedef struct VkRowBox {
+    int64_t src_row, dst_row, src_stride_b, src_stride_t, dst_stride_b, dst_stride_t;
+    int32_t nb, nt, ns, reserved;
+} VkRowBox;
+typedef struct VkRowBoxes {
+    int32_t n, reserved;
+    VkRowBox box[VK_RESHARD_MAX_BOXES];
+} VkRowBoxes;
+int vk_copy_row_boxes(const void* src, void* dst, const VkRowBoxes* boxes /* HOST memory */, int64_t src_rows, int64_t dst_rows,
+                      int32_t row_bytes, void* stream);
+
 /* library info */
 int vk_abi_version(void);
 /* ABI v7: the 16-bit storage type this library was built for: 0 = bf16 (libvista_hip.so, the default and the BASELINE config's dtype), 1 = IEEE fp16

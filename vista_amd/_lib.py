@@ -57,7 +57,19 @@ class VkGemmDesc(C.Structure):
     ]
 
 
-ABI_VERSION = 8  # vk_abi_version() of the library this table mirrors
+VK_RESHARD_MAX_BOXES = 32
+
+
+class VkRowBox(C.Structure):
+    _fields_ = [("src_row", _i64), ("dst_row", _i64), ("src_stride_b", _i64), ("src_stride_t", _i64), ("dst_stride_b", _i64), ("dst_stride_t", _i64),
+                ("nb", _i32), ("nt", _i32), ("ns", _i32), ("reserved", _i32)]
+
+
+class VkRowBoxes(C.Structure):
+    _fields_ = [("n", _i32), ("reserved", _i32), ("box", VkRowBox * VK_RESHARD_MAX_BOXES)]
+
+
+ABI_VERSION = 9  # vk_abi_version() of the library this table mirrors
 
 # name -> argtypes; every entry returns int. Must list every symbol include/vista_hip.h declares
 # (tests/test_abi.py checks the header against this table and against the built library).
@@ -111,6 +123,7 @@ SIGNATURES = {
     "vk_ensemble_variance_sum": [_vp, _vp, _vp, _i32, _i64, _vp],
     "vk_lanczos_resize_u8": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "vk_frames_to_u8": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "vk_copy_row_boxes": [_vp, _vp, C.POINTER(VkRowBoxes), _i64, _i64, _i32, _vp],
     "vk_abi_version": [],
     "vk_act_dtype": [],
 }

@@ -1278,3 +1278,37 @@ def frames_to_u8(x, real=False, grid=False):
         out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=x.device)
     check(_lib.load().vk_frames_to_u8(_p(x), _p(out), n, H, W, xmaps, pad, 1 if real else 0, _stream()), "vk_frames_to_u8")
     return out
+
+
+# ---- exchange packing of the frame-sharded step (csrc/reshard.hip, ABI v9) ----
+def row_boxes(boxes):
+    """A list of (src_row, dst_row, src_stride_b, src_stride_t, dst_stride_b, dst_stride_t, nb, nt, ns) tuples -> the VkRowBoxes the library
+    reads. n is the list's length whatever it is (the library refuses 0 and more than VK_RESHARD_MAX_BOXES); boxes past the struct's capacity
+    are not stored."""
+    rb = _lib.VkRowBoxes()
+    rb.n = len(boxes)
+    for i, b in enumerate(boxes[:_lib.VK_RESHARD_MAX_BOXES]):
+        if len(b) != 9:
+            raise ValueError(f"row_boxes: box {i} has {len(b)} entries, expected 9 (src_row, dst_row, four strides, nb, nt, ns)")
+        rb.box[i] = _lib.VkRowBox(*[int(v) for v in b], 0)
+    return rb
+
+
+def copy_row_boxes(src, dst, boxes):
+    """vk_copy_row_boxes: copy the strided row boxes of a plan from src (src_rows, C) into dst (dst_rows, C) in one launch, on the current stream.
+    src and dst are 2-D views of one dtype and one row width with dense rows; `boxes` is a list of 9-tuples (row_boxes) or a prebuilt
+    VkRowBoxes. The destination rows of a plan must not overlap. Rows dst is not told to write keep their contents."""
+    if src.dim() != 2 or dst.dim() != 2:
+        raise ValueError(f"copy_row_boxes: expected 2-D (rows, C) views, got {tuple(src.shape)} and {tuple(dst.shape)}")
+    if src.dtype != dst.dtype:
+        raise ValueError(f"copy_row_boxes: src is {src.dtype}, dst is {dst.dtype}")
+    if src.shape[1] != dst.shape[1]:
+        raise ValueError(f"copy_row_boxes: row widths differ: src {src.shape[1]}, dst {dst.shape[1]}")
+    if not (src.is_contiguous() and dst.is_contiguous()):
+        raise ValueError("copy_row_boxes: src and dst must have dense rows (contiguous 2-D views)")
+    if not (src.is_cuda and dst.is_cuda):
+        raise _lib.VistaHipError("copy_row_boxes: tensors must live on the GPU (vista_amd has no CPU / eager fallback)")
+    rb = boxes if isinstance(boxes, _lib.VkRowBoxes) else row_boxes(boxes)
+    check(_lib.load().vk_copy_row_boxes(_p(src), _p(dst), C.byref(rb), src.shape[0], dst.shape[0], src.shape[1] * src.element_size(),
+                                        _stream()), "vk_copy_row_boxes")
+    return dst

@@ -17,9 +17,17 @@ half.
 Communicators: `DistComm` wraps torch.distributed (backend "nccl" = RCCL on ROCm; "gloo" in the CPU tests);
 `ThreadComm` runs P ranks as threads of one process (used to validate the sharded numerics on a single GPU).
 """
+import os
 import threading
 
 import torch
+
+# The row gathers / scatters around every exchange (FrameShard below) run as ONE strided-box copy kernel each (ops.copy_row_boxes,
+# csrc/reshard.hip) for GPU tensors whose rows are a multiple of 16 bytes; every other tensor -- CPU tensors, odd widths -- takes torch's
+# index_select / index_copy_ / cat. The switch is VISTA_RESHARD_HIP=1 (or parallel.HIP_RESHARD = True); it is OFF by default until the rank-step
+# A/B against the torch calls (tools/rank_proxy.py) has been recorded under profiles/ -- nobody has timed the kernel inside a step yet. Either
+# way the operation is a copy: the results are the same bit for bit (tests/test_reshard_gpu.py runs both).
+HIP_RESHARD = os.environ.get("VISTA_RESHARD_HIP", "0") == "1"
 
 
 def split_counts(n, parts):
@@ -210,9 +218,76 @@ class ThreadComm:
         return [g.clone() for g in got]
 
 
-def _rows(t, index):
-    """Row gather of an exchange plan; None = the identity (the tensor itself, made contiguous if it is not)."""
-    return t.contiguous() if index is None else t.index_select(0, index)
+def _box(src_row, dst_row, src_stride_b, src_stride_t, dst_stride_b, dst_stride_t, nb, nt, ns):
+    """One strided box of an exchange plan (include/vista_hip.h, VkRowBox): rows (b, t, s) go from src_row + b*src_stride_b + t*src_stride_t + s
+    to dst_row + b*dst_stride_b + t*dst_stride_t + s. A box of no rows is written with all extents 0."""
+    if nb == 0 or nt == 0 or ns == 0:
+        return (0, 0, 0, 0, 0, 0, 0, 0, 0)
+    return (src_row, dst_row, src_stride_b, src_stride_t, dst_stride_b, dst_stride_t, nb, nt, ns)
+
+
+def _box_rows(boxes):
+    return sum(b[6] * b[7] * b[8] for b in boxes)
+
+
+def _boxes_identity(boxes):
+    """Does this gather leave every row where it is? The destination rows of a plan never repeat and cover the output, so box by box is enough."""
+    return all(b[8] == 0 or (b[0] == b[1] and (b[6] == 1 or b[2] == b[4]) and (b[7] == 1 or b[3] == b[5])) for b in boxes)
+
+
+class _Plan(dict):
+    """An exchange plan. The boxes, the row counts ("rows") and which gathers are the identity ("identity") are there from the start; the
+    int64 index tensors (the torch path of CPU tensors and odd row widths) are built by `build_index` when one of them is first asked for:
+    a step that packs with the HIP kernel never builds them (at S = 9216 they are several MB each)."""
+
+    def __init__(self, items, build_index):
+        super().__init__(items)
+        self["rows"] = {k: _box_rows(v) for k, v in self["boxes"].items()}
+        self["identity"] = {k: _boxes_identity(v) for k, v in self["boxes"].items()}
+        self._build_index = build_index
+
+    def __missing__(self, key):
+        if self._build_index is not None:
+            build, self._build_index = self._build_index, None
+            self.update(build())
+        return dict.__getitem__(self, key)
+
+
+def _hip_rows(*views):
+    """Do these (rows, C) views take the HIP packing kernel? GPU tensors with dense, 16-byte aligned rows of a multiple of 16 bytes."""
+    return HIP_RESHARD and all(t.is_cuda and t.shape[0] > 0 and t.is_contiguous() and (t.shape[1] * t.element_size()) % 16 == 0
+                               and t.shape[1] > 0 and t.data_ptr() % 16 == 0 for t in views)
+
+
+def _cboxes(pl, name):
+    """The VkRowBoxes struct of plan entry `name`, built on first use and kept with the plan."""
+    cache = pl.setdefault("_c", {})
+    if name not in cache:
+        from . import ops
+        cache[name] = ops.row_boxes(pl["boxes"][name])
+    return cache[name]
+
+
+def _index(pl, name, device):
+    """The index tensor of plan entry `name` on `device` (the torch path; plans keep it on the host until a GPU tensor asks for it)."""
+    ix = pl[name]
+    if ix.device == device:
+        return ix
+    cache = pl.setdefault("_dev", {})
+    if name not in cache:
+        cache[name] = ix.to(device)
+    return cache[name]
+
+
+def _rows(t, pl, name):
+    """Row gather of an exchange plan; a plan entry of None = the identity (the tensor itself, made contiguous if it is not)."""
+    if pl["identity"][name]:
+        return t.contiguous()
+    n_out = pl["rows"][name]
+    if n_out and _hip_rows(t):
+        from . import ops
+        return ops.copy_row_boxes(t, torch.empty((n_out, t.shape[1]), dtype=t.dtype, device=t.device), _cboxes(pl, name))
+    return t.index_select(0, _index(pl, name, t.device))
 
 
 class FrameShard:
@@ -242,7 +317,6 @@ class FrameShard:
         # VISTA_A2A_CHUNKS = n > 1 (opt-in, default 1): the temporal block runs on n pixel sub-ranges of the rank's slice in turn and each
         # sub-range's way back to the frame layout is its own all-to-all, started asynchronously -- the exchange of sub-range i runs under
         # the compute of sub-range i + 1 (SURVEY 8e "overlap"). Same result bit for bit: the temporal block is pointwise in space.
-        import os
         self.a2a_chunks = max(1, int(os.environ.get("VISTA_A2A_CHUNKS", "1")))
 
     # global image ids (b*T + t) of this rank's frames, in local (b, t_local) order
@@ -250,15 +324,37 @@ class FrameShard:
         t0 = self.t_off[self.rank]
         return [b * self.T + t0 + i for b in range(self.B) for i in range(self.t_local)]
 
+    def local_rows_boxes(self):
+        """local_image_ids() as a box plan over the rows of a (B*T, ...) tensor."""
+        return [_box(self.t_off[self.rank], 0, self.T, 0, self.t_local, 0, self.B, 1, self.t_local)]
+
     def pixel_counts(self, S):
         return split_counts(S, self.P)
 
-    # ---- exchanges. Packing / unpacking is one row gather each (cached int64 index tensors), so an exchange is
-    #      gather -> all-to-all -> gather regardless of the number of ranks.
+    # ---- exchanges. Packing / unpacking is one row gather each, so an exchange is gather -> all-to-all -> gather regardless of the number of
+    #      ranks. A plan holds every gather twice: as at most P strided boxes ("boxes": one per peer, the form the HIP kernel takes by value)
+    #      and as an int64 index tensor (the torch path of CPU tensors and odd row widths), built when that path first needs it (_Plan).
     def _plan(self, S, device):
         key = (S, str(device))
         if key in self._plans:
             return self._plans[key]
+        B, P, r, T, t_l = self.B, self.P, self.rank, self.T, self.t_local
+        sc = self.pixel_counts(S)
+        so = offsets(sc)
+        s_r = sc[r]
+        ro = offsets([B * self.t_counts[q] * s_r for q in range(P)])   # receive offsets of to_pixels / send offsets of to_frames, in rows
+        ro2 = offsets([B * t_l * sc[q] for q in range(P)])             # and of the way back
+        tc, to = self.t_counts, self.t_off
+        boxes = {   # the four gathers, peer by peer (q): send / receive blocks are dense (b, t, s) arrays, the tensors strided views of them
+            "pack_fp": [_box(so[q], B * t_l * so[q], t_l * S, S, t_l * sc[q], sc[q], B, t_l, sc[q]) for q in range(P)],
+            "unpack_fp": [_box(ro[q], to[q] * s_r, tc[q] * s_r, s_r, T * s_r, s_r, B, tc[q], s_r) for q in range(P)],
+            "pack_pf": [_box(to[q] * s_r, ro[q], T * s_r, s_r, tc[q] * s_r, s_r, B, tc[q], s_r) for q in range(P)],
+            "unpack_pf": [_box(ro2[q], so[q], t_l * sc[q], sc[q], t_l * S, S, B, t_l, sc[q]) for q in range(P)]}
+        plan = self._plans[key] = _Plan({"sc": sc, "s_r": s_r, "boxes": boxes}, lambda: self._plan_index(S))
+        return plan
+
+    def _plan_index(self, S):
+        """The four gathers of _plan(S) as index tensors; None = the identity."""
         B, P, r, T, t_l = self.B, self.P, self.rank, self.T, self.t_local
         sc = self.pixel_counts(S)
         so = offsets(sc)
@@ -285,12 +381,8 @@ class FrameShard:
         # to_pixels IS the result and the send buffer of to_frames IS the input; only the frame-sharded side needs its row gather.
         def ident(ix):
             ix = ix.reshape(-1)
-            return None if torch.equal(ix, ar(ix.numel())) else ix.to(device)
-        plan = {"sc": sc, "s_r": s_r,
-                "pack_fp": ident(pack_fp), "unpack_fp": ident(unpack_fp),
-                "pack_pf": ident(pack_pf), "unpack_pf": ident(unpack_pf)}
-        self._plans[key] = plan
-        return plan
+            return None if torch.equal(ix, ar(ix.numel())) else ix
+        return {"pack_fp": ident(pack_fp), "unpack_fp": ident(unpack_fp), "pack_pf": ident(pack_pf), "unpack_pf": ident(unpack_pf)}
 
     def exchange_splits(self, S, C, rank=None):
         """Element counts per peer of the three all_to_all_single calls of a block pair, for `rank` (default: this rank):
@@ -390,11 +482,11 @@ class FrameShard:
         assert n == B * self.t_local
         pl = self._plan(S, x.device)
         sc, s_r = pl["sc"], pl["s_r"]
-        send = _rows(x.reshape(n * S, C), pl["pack_fp"])
+        send = _rows(x.reshape(n * S, C), pl, "pack_fp")
         in_splits, out_splits = self.exchange_splits(S, C)["to_pixels"]
         recv = torch.empty(sum(out_splits), dtype=x.dtype, device=x.device)
         self.comm.all_to_all(recv, send.reshape(-1), out_splits, in_splits)
-        return _rows(recv.view(-1, C), pl["unpack_fp"]).view(B * self.T, s_r, C)
+        return _rows(recv.view(-1, C), pl, "unpack_fp").view(B * self.T, s_r, C)
 
     def to_frames(self, y, S):
         """(B*T, S_r, C) pixel-sharded -> (B*t_local, S, C) frame-sharded."""
@@ -404,11 +496,11 @@ class FrameShard:
         pl = self._plan(S, y.device)
         sc = pl["sc"]
         assert s_r == pl["s_r"]
-        send = _rows(y.reshape(n * s_r, C), pl["pack_pf"])
+        send = _rows(y.reshape(n * s_r, C), pl, "pack_pf")
         in_splits, out_splits = self.exchange_splits(S, C)["to_frames"]
         recv = torch.empty(sum(out_splits), dtype=y.dtype, device=y.device)
         self.comm.all_to_all(recv, send.reshape(-1), out_splits, in_splits)
-        return _rows(recv.view(-1, C), pl["unpack_pf"]).view(B * self.t_local, S, C)
+        return _rows(recv.view(-1, C), pl, "unpack_pf").view(B * self.t_local, S, C)
 
     # ---- chunked way back (pixels -> frames) for compute / transport overlap
     def pixel_chunks(self, S, chunks):
@@ -428,16 +520,23 @@ class FrameShard:
         cc = [sub[q][c] for q in range(P)]                              # width of sub-range c on rank q
         co = [offsets(sub[q])[c] for q in range(P)]                     # its offset inside q's slice
         n_c = cc[self.rank]
-        ar = torch.arange
-        # send: for q, rows (b, t in q's frames, s) of y viewed (B*T*n_c, C)
-        pack = torch.cat([((ar(B)[:, None, None] * T + (self.t_off[q] + ar(self.t_counts[q]))[None, :, None]) * n_c + ar(n_c)[None, None, :]).reshape(-1)
-                          for q in range(P)]) if n_c else torch.empty(0, dtype=torch.int64)
-        # received: for q, rows (b, t_local, s in q's sub-range) -> rows of the frame-sharded result viewed (B*t_l*S, C)
-        dest = torch.cat([((ar(B)[:, None, None] * t_l + ar(t_l)[None, :, None]) * S + (so[q] + co[q] + ar(cc[q]))[None, None, :]).reshape(-1)
-                          for q in range(P)])
-        pl = {"n_c": n_c, "pack": pack.to(device), "dest": dest.to(device),
-              "in_rows": [B * self.t_counts[q] * n_c for q in range(P)], "out_rows": [B * t_l * cc[q] for q in range(P)]}
-        self._plans[key] = pl
+        in_rows, out_rows = [B * self.t_counts[q] * n_c for q in range(P)], [B * t_l * cc[q] for q in range(P)]
+        ro = offsets(out_rows)
+        tc, to = self.t_counts, self.t_off
+        boxes = {"pack": [_box(to[q] * n_c, B * to[q] * n_c, T * n_c, n_c, tc[q] * n_c, n_c, B, tc[q], n_c) for q in range(P)],
+                 "dest": [_box(ro[q], so[q] + co[q], t_l * cc[q], cc[q], t_l * S, S, B, t_l, cc[q]) for q in range(P)]}   # a scatter: dst = rows of `out`
+
+        def index():
+            ar = torch.arange
+            # send: for q, rows (b, t in q's frames, s) of y viewed (B*T*n_c, C)
+            pack = torch.cat([((ar(B)[:, None, None] * T + (to[q] + ar(tc[q]))[None, :, None]) * n_c + ar(n_c)[None, None, :]).reshape(-1)
+                              for q in range(P)]) if n_c else torch.empty(0, dtype=torch.int64)
+            # received: for q, rows (b, t_local, s in q's sub-range) -> rows of the frame-sharded result viewed (B*t_l*S, C)
+            dest = torch.cat([((ar(B)[:, None, None] * t_l + ar(t_l)[None, :, None]) * S + (so[q] + co[q] + ar(cc[q]))[None, None, :]).reshape(-1)
+                              for q in range(P)])
+            return {"pack": pack, "dest": dest}
+        pl = self._plans[key] = _Plan({"n_c": n_c, "boxes": boxes, "in_rows": in_rows, "out_rows": out_rows}, index)
+        pl["identity"]["pack"] = False   # (the chunked way back always gathers: its send buffer is a fresh tensor the exchange may hold on to)
         return pl
 
     def to_frames_begin(self, y, S, chunks, c):
@@ -446,7 +545,7 @@ class FrameShard:
         n, n_c, C = y.shape
         pl = self._chunk_plan(S, chunks, c, y.device)
         assert n == self.B * self.T and n_c == pl["n_c"]
-        send = y.reshape(n * n_c, C).index_select(0, pl["pack"])
+        send = _rows(y.reshape(n * n_c, C), pl, "pack")
         recv = torch.empty(sum(pl["out_rows"]) * C, dtype=y.dtype, device=y.device)
         work = self.comm.all_to_all(recv, send.reshape(-1), [r * C for r in pl["out_rows"]], [r * C for r in pl["in_rows"]], async_op=True)
         return (work, recv, send, pl, C)  # (send is kept alive until the exchange has been waited for)
@@ -456,8 +555,21 @@ class FrameShard:
         work, recv, _send, pl, C = pending
         if work is not None and hasattr(work, "wait"):
             work.wait()
-        out.view(-1, C).index_copy_(0, pl["dest"], recv.view(-1, C))
+        o2, r2 = out.view(-1, C), recv.view(-1, C)
+        if _hip_rows(r2, o2):
+            from . import ops
+            ops.copy_row_boxes(r2, o2, _cboxes(pl, "dest"))
+        else:
+            o2.index_copy_(0, _index(pl, "dest", out.device), r2)
         return out
+
+    def halo_boxes(self, S):
+        """The send buffer of halo_exchange as a box plan over h viewed (B*t_local*S, C): every clip's first frame (for rank r - 1), then every
+        clip's last frame (for rank r + 1); an end of the window sends nothing that way."""
+        B, t_l, r = self.B, self.t_local, self.rank
+        first = _box(0, 0, t_l * S, 0, S, 0, B, 1, S)
+        last = _box((t_l - 1) * S, B * S if r > 0 else 0, t_l * S, 0, S, 0, B, 1, S)
+        return ([first] if r > 0 else []) + ([last] if r < self.P - 1 else [])
 
     def halo_exchange(self, h):
         """Frame-sharded temporal conv support: h (B*t_local, S, C) -> (prev, next), each (B, S, C): the neighbour ranks' last /
@@ -469,12 +581,21 @@ class FrameShard:
         h4 = h.view(B, t_l, S, C)
         fs = B * S * C
         in_splits, out_splits = self.exchange_splits(S, C)["halo"]
-        parts = []
-        if r > 0:
-            parts.append(h4[:, 0].reshape(-1))
-        if r < P - 1:
-            parts.append(h4[:, t_l - 1].reshape(-1))
-        send = torch.cat(parts) if parts else h.new_empty(0)
+        n_send = (r > 0) + (r < P - 1)
+        h2 = h4.view(n * S, C)
+        if n_send and _hip_rows(h2):   # first frame (towards r - 1) then last frame (towards r + 1) of every clip, one launch
+            from . import ops
+            pl = self._plans.get(("halo", S))
+            if pl is None:
+                pl = self._plans[("halo", S)] = {"boxes": {"halo": self.halo_boxes(S)}}
+            send = ops.copy_row_boxes(h2, torch.empty((n_send * B * S, C), dtype=h.dtype, device=h.device), _cboxes(pl, "halo")).view(-1)
+        else:
+            parts = []
+            if r > 0:
+                parts.append(h4[:, 0].reshape(-1))
+            if r < P - 1:
+                parts.append(h4[:, t_l - 1].reshape(-1))
+            send = torch.cat(parts) if parts else h.new_empty(0)
         recv = torch.empty(sum(out_splits), dtype=h.dtype, device=h.device)
         self.comm.all_to_all(recv, send, out_splits, in_splits)
         prev = recv[:fs].view(B, S, C) if r > 0 else None
@@ -489,7 +610,18 @@ class FrameShard:
         return torch.cat(self.comm.all_gather_list(x_local, self.t_counts), 0)
 
     def take_local_rows(self, full):
-        """Rows of a (B*T, ...) replicated tensor that belong to this rank's images, in local order."""
+        """Rows of a (B*T, ...) replicated tensor that belong to this rank's images, in local order. A dense GPU tensor with 16-byte-multiple
+        rows goes through the packing kernel (one box); anything else -- a CPU tensor, an odd width, a view -- through index_select."""
+        if full.is_contiguous() and full.dim() >= 1 and full.shape[0] == self.B * self.T:
+            f2 = full.view(full.shape[0], -1)
+            if _hip_rows(f2):   # frames [t0, t0 + t_local) of every clip: one box
+                from . import ops
+                pl = self._plans.get("local_rows")
+                if pl is None:
+                    pl = self._plans["local_rows"] = {"boxes": {"rows": self.local_rows_boxes()}}
+                out = torch.empty((self.B * self.t_local,) + tuple(full.shape[1:]), dtype=full.dtype, device=full.device)
+                ops.copy_row_boxes(f2, out.view(out.shape[0], -1), _cboxes(pl, "rows"))
+                return out
         key = str(full.device)
         cache = self.__dict__.setdefault("_local_rows_idx", {})
         if key not in cache:  # built once: torch.tensor(list, device=cuda) is a blocking host->device copy (6 ms mid-step)

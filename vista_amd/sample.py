@@ -7,6 +7,11 @@ launches every kernel of every step from the host instead.
 
     python -m vista_amd.sample --ckpt ckpts/vista.safetensors --dataset IMG --data_root image_folder --save outputs
 
+Several GPUs: start one process per GPU with `python -m torch.distributed.run --nproc-per-node=N -m vista_amd.sample ...` (same flags). With
+WORLD_SIZE > 1 in the environment `main` runs as one rank of the job: the denoising steps are frame-sharded over the ranks
+(vista_amd/parallel.py; VISTA_SHARD = hybrid | frames, VISTA_DIST_BACKEND = nccl | gloo), everything around them is replicated, and
+rank 0 writes the files.
+
 `run(...)` is the loop body as a function (returns the tensors instead of writing files), `main(argv)` the loop of sample.py:204-274.
 """
 import argparse
@@ -94,11 +99,14 @@ class _StageClock:
 
 
 def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames=25, n_rounds=1, n_conds=1, n_steps=50, cfg_scale=2.5,
-        cond_aug=0.0, eager=False, timings=None):
+        cond_aug=0.0, eager=False, timings=None, shard=None):
     """One sample of the reference's loop (sample.py:222-254) without the files -> (samples in [0, 1], samples_z, inputs in [-1, 1]): load and
     resize the frames, build the value dict, pick the guider (TrianglePredictionGuider for a rollout, VanillaCFG for one round), do_sample.
     The caller seeds. `timings` (a dict) receives the wall time in seconds of load, condition, encode, decode and sample (= the rest of do_sample:
-    the denoising loops)."""
+    the denoising loops).
+    `shard` (a vista_amd.parallel.FrameShard, one per rank, every rank calling with the same arguments and the same seed): the denoising steps
+    run frame-sharded over the shard's ranks, eagerly on one stream whatever `eager` says (a captured graph cannot hold the collectives: DESIGN
+    section 6). Conditioner, encoder, decoder and the noise are replicated: every rank returns the same tensors."""
     t0 = time.perf_counter()
     images = SU.load_img_seq(frame_list, height, width, "cuda")
     torch.cuda.synchronize()
@@ -113,7 +121,9 @@ def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames
         value_dict[key] = value
     sampler = SU.init_sampling(guider="TrianglePredictionGuider" if n_rounds > 1 else "VanillaCFG", steps=n_steps, cfg_scale=cfg_scale,
                                num_frames=n_frames)
-    sampler.graph = sampler.cfg_streams = not eager   # (one GPU, no frame shard)
+    sampler.graph = sampler.cfg_streams = not eager and shard is None   # (graph replay: one GPU, no frame shard)
+    if shard is not None:
+        sampler.shard = shard
     import contextlib
     stages = {}
     with (_StageClock(model, stages) if timings is not None else contextlib.nullcontext()):
@@ -127,12 +137,63 @@ def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames
     return out
 
 
+def init_distributed(n_frames):
+    """This process as one rank of a torch.distributed.run job (WORLD_SIZE > 1): picks the GPU (VISTA_FORCE_DEVICE, else LOCAL_RANK), joins the
+    process group (VISTA_DIST_BACKEND, default "nccl" = RCCL), builds this rank's FrameShard (VISTA_SHARD = "hybrid" (default) | "frames") and
+    runs its plumbing check -- every collective signature of a sharded step on tiny tensors -- before any model is built.
+    -> (global rank, shard). The caller owns the process group (destroy_process_group)."""
+    import torch.distributed as dist
+    from .parallel import DistComm, make_shard
+    world, rank = int(os.environ["WORLD_SIZE"]), int(os.environ.get("RANK", "0"))
+    mode = os.environ.get("VISTA_SHARD") or "hybrid"
+    if mode not in ("hybrid", "frames"):
+        raise ValueError(f"VISTA_SHARD must be 'hybrid' or 'frames', not {mode!r}")
+    group_size = world // 2 if (mode == "hybrid" and world % 2 == 0) else world
+    if group_size > n_frames:
+        raise ValueError(f"WORLD_SIZE {world} (VISTA_SHARD={mode}) puts {group_size} ranks into one frame-shard group, but --n_frames is "
+                         f"{n_frames}: a rank needs at least one frame")
+    backend = os.environ.get("VISTA_DIST_BACKEND", "nccl")
+    dev = int(os.environ.get("VISTA_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    torch.cuda.set_device(dev)
+    if backend == "nccl":
+        dist.init_process_group("nccl", device_id=torch.device("cuda", dev))   # "nccl" is RCCL on ROCm
+    else:
+        dist.init_process_group(backend)
+    try:
+        def make_group(ranks):   # collective: every rank creates every group, members get a communicator
+            g = dist.new_group(ranks=ranks)
+            return DistComm(g) if rank in ranks else None
+        shard = make_shard(n_frames, world, rank, mode=mode, make_group=make_group)
+        try:
+            shard.selfcheck(torch.device("cuda", dev))
+        except Exception as e:  # noqa: BLE001
+            raise RuntimeError(f"[rank {rank}/{world}] multi-GPU plumbing check failed (VISTA_SHARD={mode}, backend {backend}, "
+                               f"device cuda:{dev}): {e}") from e
+    except BaseException:
+        dist.destroy_process_group()
+        raise
+    return rank, shard
+
+
 def main(argv=None):
     opt, _unknown = parse_args(prog="python -m vista_amd.sample").parse_known_args(argv)
     # sizes the kernels cannot take are refused here, before 2.5 billion parameters are built
     net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
     SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, net_params)
-    if opt.low_vram:
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:   # one rank of a torch.distributed.run job
+        rank, shard = init_distributed(opt.n_frames)
+        try:
+            return _sample_loop(opt, shard, rank)
+        finally:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+    return _sample_loop(opt, None, 0)
+
+
+def _sample_loop(opt, shard, rank):
+    """The loop of sample.py:204-274. Every rank of a job walks the same sample indices (the walk is a function of the seed); rank 0 writes."""
+    if opt.low_vram and rank == 0:
         print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
     spec = dict(SU.VERSION2SPECS[opt.version])
     if opt.config:
@@ -150,13 +211,14 @@ def main(argv=None):
         timings = {}
         samples, samples_z, inputs = run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames,
                                          n_rounds=opt.n_rounds, n_conds=opt.n_conds, n_steps=opt.n_steps, cfg_scale=opt.cfg_scale,
-                                         cond_aug=opt.cond_aug, eager=opt.eager, timings=timings)
-        t0 = time.perf_counter()
-        for path, frames in ((virtual_path, samples), (real_path, inputs)):
-            for mode in ("videos", "grids", "images"):
-                SU.perform_save_locally(path, frames, mode, opt.dataset, sample_index)
-        timings["save"] = time.perf_counter() - t0
-        print(f"sample {sample_index}: " + ", ".join(f"{k} {v:.2f} s" for k, v in timings.items()), flush=True)
+                                         cond_aug=opt.cond_aug, eager=opt.eager, timings=timings, shard=shard)
+        if rank == 0:
+            t0 = time.perf_counter()
+            for path, frames in ((virtual_path, samples), (real_path, inputs)):
+                for mode in ("videos", "grids", "images"):
+                    SU.perform_save_locally(path, frames, mode, opt.dataset, sample_index)
+            timings["save"] = time.perf_counter() - t0
+            print(f"sample {sample_index}: " + ", ".join(f"{k} {v:.2f} s" for k, v in timings.items()), flush=True)
 
         if opt.rand_gen:
             sample_index += random.randint(1, max(1, dataset_length - 1))
