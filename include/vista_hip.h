@@ -388,6 +388,35 @@ int vk_lanczos_resize_u8(const void* src, void* tmp, float* out, const int32_t* 
  *   (torchvision.utils.make_grid with pad_value 0, written straight from the NCHW tensor). out 4-byte aligned. */
 int vk_frames_to_u8(const float* x, void* out, int32_t n_img, int32_t H, int32_t W, int32_t xmaps, int32_t pad, int32_t real, void* stream);
 
+/* ------------------------------------------------------------------ reward estimation front door (csrc/reward.hip)
+ * Added under ABI v9 without a version step: the two entry points are purely additive (no existing signature, struct or meaning changes), so
+ * vk_abi_version() stays 9. Storage-type independent: the same code is linked into both libraries.
+ *
+ * vk_ensemble_frame_stats: where in the window, and where in the picture, the E ensemble members of a reward run disagree.
+ *   x          [E][T][C][hw] fp32 (the sampler's own output type), dense. 2 <= E <= 64.
+ *   v[t][c][p] = the unbiased ensemble variance of one element, in the arithmetic of vk_ensemble_variance_sum operation for operation: the fp32
+ *                mean summed in member order and divided by E, an fmaf chain of squared differences in member order, divided by E - 1.
+ *   frame_sum  [T] fp64: sum of v over the frame's C * hw elements. Every frame is reduced by VK_FRAME_STATS_BLOCKS workgroups whose element
+ *              assignment is a function of hw alone, then one thread adds the frame's partials in block order: no atomics, bitwise repeatable,
+ *              and a frame's sum does not change with T or with the frames around it.
+ *   map        [T][hw] fp32 or NULL: mean over C of v, summed in channel order and divided by C.
+ *   partial_ws T * VK_FRAME_STATS_BLOCKS doubles of scratch, the caller's.
+ *   Where hw % 4 == 0 the kernel moves 16 bytes per lane: x (and map, when given) must then be 16-byte aligned; any other hw takes any alignment.
+ *   VK_EINVAL: E < 2, E > 64, T / C / hw <= 0, T > 65535, a NULL x / frame_sum / partial_ws, a misaligned pointer where hw % 4 == 0. */
+#define VK_FRAME_STATS_BLOCKS 16
+int vk_ensemble_frame_stats(const float* x, double* frame_sum, float* map, double* partial_ws, int32_t E, int32_t T, int32_t C, int32_t hw,
+                            void* stream);
+/* vk_heat_overlay_u8: the input frames with a per-cell map blended in as a heat colour, ready to be written as 8-bit pictures.
+ *   frames (n_img, 3, H, W) fp32 in [-1, 1] (16-byte aligned); map (n_img, H / cell, W / cell) fp32, >= 0; out (n_img, H, W, 3) uint8 (4-byte aligned).
+ *   f   = 255 * (x + 1) / 2, the float vk_frames_to_u8(real = 1) forms before its cast
+ *   a   = alpha * min(1, map[t][y / cell][x / cell] * inv_vmax)
+ *   out = uint8(f + a * (K - f)),  K = (255, 32, 0) per channel; the cast truncates.
+ *   Every operation is rounded once in fp32 and nothing is contracted into an FMA: the bytes equal numpy's float32 evaluation of the expression.
+ *   VK_EINVAL: a NULL or misaligned pointer, n_img / H / W / cell <= 0, H % cell or W % cell != 0, alpha outside [0, 1], inv_vmax negative or
+ *   not finite. */
+int vk_heat_overlay_u8(const float* frames, const float* map, void* out, int32_t n_img, int32_t H, int32_t W, int32_t cell, float inv_vmax,
+                       float alpha, void* stream);
+
 /* ------------------------------------------------------------------ exchange packing of the frame-sharded step (ABI v9; csrc/reshard.hip)
  * Storage-type independent: the same code is linked into both libraries.
  *

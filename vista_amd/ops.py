@@ -1280,6 +1280,56 @@ def frames_to_u8(x, real=False, grid=False):
     return out
 
 
+# ---- reward estimation front door (csrc/reward.hip) ----
+FRAME_STATS_BLOCKS = 16   # VK_FRAME_STATS_BLOCKS of include/vista_hip.h: partial sums per frame in the workspace
+
+
+def _aligned16(t):
+    """A dense tensor whose first element sits on a 16-byte boundary (a dense view into another tensor's storage may not)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def ensemble_frame_stats(x, want_map=True):
+    """x (E, T, C, h, w) f32, the stacked members of a reward ensemble -> (frame_sum (T,) float64 tensor, map (T, h, w) float32 or None):
+    the unbiased ensemble variance summed over every frame's elements (fixed order, fp64) and averaged over its channels per pixel
+    (vk_ensemble_frame_stats; same per-element arithmetic as ensemble_variance_sum). Nothing is synchronised: both results stay on the GPU."""
+    _need(x, F32, "x")
+    if x.dim() != 5:
+        raise ValueError(f"ensemble_frame_stats: expected (E, T, C, h, w) latents, got {tuple(x.shape)}")
+    x = _aligned16(x)
+    E, T, Cn, h, w = x.shape
+    frame_sum = torch.empty(max(T, 1), dtype=torch.float64, device=x.device)[:T]
+    ws = torch.empty(max(T, 1) * FRAME_STATS_BLOCKS, dtype=torch.float64, device=x.device)
+    fmap = torch.empty((T, h, w), dtype=F32, device=x.device) if want_map else None
+    check(_lib.load().vk_ensemble_frame_stats(_p(x), _p(frame_sum), _p(fmap), _p(ws), E, T, Cn, h * w, _stream()), "vk_ensemble_frame_stats")
+    return frame_sum, fmap
+
+
+def heat_overlay_u8(frames, fmap, vmax, alpha=0.6):
+    """frames (n, 3, H, W) f32 in [-1, 1] and fmap (n, H / cell, W / cell) f32 >= 0 -> (n, H, W, 3) uint8: every frame blended towards the heat
+    colour (255, 32, 0) with weight alpha * min(1, fmap / vmax) of its cell (vk_heat_overlay_u8; a zero map gives frames_to_u8(real=True)'s
+    bytes). 1 / vmax is formed here in float32; cell = H / fmap.shape[1] must be the same whole number along both axes."""
+    import numpy as np
+    _need(frames, F32, "frames")
+    _need(fmap, F32, "fmap")
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError(f"heat_overlay_u8: expected (n, 3, H, W) fp32 frames, got {tuple(frames.shape)}")
+    n, _, H, W = frames.shape
+    if fmap.dim() != 3 or fmap.shape[0] != n or fmap.shape[1] <= 0 or fmap.shape[2] <= 0:
+        raise ValueError(f"heat_overlay_u8: expected a (n, H / cell, W / cell) map for {n} frames, got {tuple(fmap.shape)}")
+    cell = H // fmap.shape[1]
+    if cell <= 0 or cell * fmap.shape[1] != H or cell * fmap.shape[2] != W:
+        raise ValueError(f"heat_overlay_u8: a {tuple(fmap.shape[1:])} map does not tile {H} x {W} frames with square cells")
+    if not float(vmax) > 0.0:
+        raise ValueError(f"heat_overlay_u8: vmax must be positive, got {vmax}")
+    inv_vmax = float(np.float32(1) / np.float32(vmax))
+    frames, fmap = _aligned16(frames), fmap.contiguous()
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=frames.device)
+    check(_lib.load().vk_heat_overlay_u8(_p(frames), _p(fmap), _p(out), n, H, W, cell, inv_vmax, float(alpha), _stream()), "vk_heat_overlay_u8")
+    return out
+
+
 # ---- exchange packing of the frame-sharded step (csrc/reshard.hip, ABI v9) ----
 def row_boxes(boxes):
     """A list of (src_row, dst_row, src_stride_b, src_stride_t, dst_stride_b, dst_stride_t, nb, nt, ns) tuples -> the VkRowBoxes the library
