@@ -253,7 +253,10 @@ int vk_softmax_rows_f32_bf16(const float* x, void* y, int64_t rows, int32_t cols
  * Replaces GroupNorm32/Normalize + nn.SiLU: vwm/modules/diffusionmodules/util.py:196-216, attention.py:141-142,
  * openaimodel.py:195-199,227-230, video_model.py:434-436.
  * stats_ws: f32 workspace of 64*(n_img/frames_per_group) + 64*n_img*ceil(S/32) floats (fixed-order partial sums:
- * results are bitwise reproducible, no atomics). */
+ * results are bitwise reproducible, no atomics). In the fp16-storage build this call and vk_groupnorm_silu_cat_bf16 take their sums about each
+ * group's first element, so that E[x^2] - mean^2 does not cancel at a large |mean| / std, and refuse y == x (VK_EINVAL: every workgroup of a
+ * group reads that element while the first one would overwrite it); the sums that cross the ABI below stay raw, so a norm fed by a GEMM
+ * epilogue's partials or by sharded statistics -- most of the UNet's ResBlock norms -- is computed as before in both builds. */
 int vk_groupnorm_silu_bf16(const void* x, void* y, const float* gamma, const float* beta, float* stats_ws,
                            int32_t n_img, int32_t S, int32_t C, int32_t frames_per_group, float eps, int32_t silu,
                            void* stream);

@@ -18,6 +18,7 @@
 namespace {
 
 constexpr int GN_TOK = 128;  // tokens per workgroup
+constexpr bool GN_PIVOT = VK_F16 != 0;  // the one-call norms of the fp16-storage build take their sums about a pivot (gn_stats_kernel)
 
 // stats pass 1: per (image, 128-token chunk) partial (sum, sumsq) of the 32 groups, reduced in a FIXED order
 // (thread partials -> LDS [r][channel] -> per-channel over r -> per-group over channels): bitwise reproducible.
@@ -25,9 +26,22 @@ constexpr int GN_TOK = 128;  // tokens per workgroup
 // materialised); every thread owns one fixed 16-B channel chunk, so the source choice is a per-thread constant.
 // AMAX (fp8 output mode of the apply pass): the workgroup also writes max|x| of its elements to amax_part[img][chunk] (plain store: no
 // atomics, nothing to clear); the apply pass reduces the partials of its image group.
-template <bool AMAX>
+//
+// PIVOT (the fp16-storage build's one-call norms): the sums are taken about a pivot, (sum (x - p), sum (x - p)^2) with p = the group's first element
+// (first image of the image group, token 0, first channel of the channel group; gn_pivot) -- the same value in every workgroup of the group, so
+// the slots still add up. The variance E[(x - p)^2] - E[x - p]^2 then cancels by (mean - p)^2 / var, a few units, instead of mean^2 / var: at
+// |mean| = 30 std the raw fp32 sums leave rstd off by 1e-3, which the fp16 output shows (2^-11) and the bf16 output (2^-8) does not. The apply
+// pass reads the same element and adds it back to the mean. Raw sums (PIVOT = false) stay the format of everything that crosses the ABI: the
+// GEMM epilogues' partials, vk_groupnorm_stats_bf16 / _apply_bf16 around the sharded all-reduce, and the whole bf16 build.
+__device__ __forceinline__ float gn_pivot(const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, int C1, int C, int S, int img0, int c0) {
+    const bool second = x2 != nullptr && c0 >= C1;
+    const int ld = x2 == nullptr ? C : (second ? C - C1 : C1);
+    return bf16_to_f32((second ? x2 + (c0 - C1) : x + c0)[((size_t)img0 * S) * ld]);
+}
+
+template <bool AMAX, bool PIVOT>
 __global__ void gn_stats_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, int C1, float* __restrict__ partial, int S, int C,
-                                int CG, int R, int tok_per_wg, float* __restrict__ amax_part) {
+                                int CG, int R, int tok_per_wg, float* __restrict__ amax_part, int frames_per_group) {
     __shared__ float wave_amax[16];
     extern __shared__ float lds[];  // [2][R][C]
     const int tid = threadIdx.x;
@@ -43,6 +57,12 @@ __global__ void gn_stats_kernel(const uint16_t* __restrict__ x, const uint16_t* 
         float sm[8], sq[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) { sm[e] = 0.f; sq[e] = 0.f; }
+        float pv[8];
+        if constexpr (PIVOT) {
+            const int img0 = (img / frames_per_group) * frames_per_group;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) pv[e] = gn_pivot(x, x2, C1, C, S, img0, ((chunk * 8 + e) / cpg) * cpg);
+        }
         const bool second = x2 != nullptr && chunk * 8 >= C1;
         const int ld = x2 == nullptr ? C : (second ? C - C1 : C1);
         const uint16_t* p = (second ? x2 + (chunk * 8 - C1) : x + chunk * 8) + ((size_t)img * S) * ld;
@@ -57,9 +77,10 @@ __global__ void gn_stats_kernel(const uint16_t* __restrict__ x, const uint16_t* 
                 unpack8(v[u], f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
+                    if (AMAX) amx = fmaxf(amx, fabsf(f[e]));
+                    if constexpr (PIVOT) f[e] -= pv[e];
                     sm[e] += f[e];
                     sq[e] = fmaf(f[e], f[e], sq[e]);
-                    if (AMAX) amx = fmaxf(amx, fabsf(f[e]));
                 }
             }
         }
@@ -69,9 +90,10 @@ __global__ void gn_stats_kernel(const uint16_t* __restrict__ x, const uint16_t* 
             unpack8(v, f);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
+                if (AMAX) amx = fmaxf(amx, fabsf(f[e]));
+                if constexpr (PIVOT) f[e] -= pv[e];
                 sm[e] += f[e];
                 sq[e] = fmaf(f[e], f[e], sq[e]);
-                if (AMAX) amx = fmaxf(amx, fabsf(f[e]));
             }
         }
 #pragma unroll
@@ -168,7 +190,8 @@ __device__ __forceinline__ void gn_st16(uint16_t* p, const uint4 v) {
 // result is bitwise that of the finalize launch it replaces. nparts <= GN_FOLD_MAX slots = at most 64 KiB read from L2 per workgroup; the finalize
 // launch it removes was 7.9 us of launch overhead per norm (105 norms per step, profiles/r05_step_kernels.txt).
 constexpr int GN_FOLD_MAX = 256;
-template <bool NTL, bool NTS, bool FOLD>
+// PIVOT: the sums are about the group's pivot element (gn_stats_kernel); the mean gets it back.
+template <bool NTL, bool NTS, bool FOLD, bool PIVOT>
 __global__ void gn_apply_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ x2, int C1, uint16_t* __restrict__ y, const float* __restrict__ gamma,
                                 const float* __restrict__ beta, const float* __restrict__ stats, int S, int C, int CG, int R,
                                 int frames_per_group, float inv_cnt, float eps, int do_silu, int tok_per_wg, int nparts) {
@@ -200,8 +223,9 @@ __global__ void gn_apply_kernel(const uint16_t* __restrict__ x, const uint16_t* 
     for (int e = 0; e < 8; ++e) {
         const int c = chunk * 8 + e;
         const int g = c / cpg;
-        const float mean = st[g] * inv_cnt;
+        float mean = st[g] * inv_cnt;
         const float var = fmaxf(st[32 + g] * inv_cnt - mean * mean, 0.f);
+        if constexpr (PIVOT) mean += gn_pivot(x, x2, C1, C, S, (img / frames_per_group) * frames_per_group, g * cpg);
         a[e] = gamma[c] * rsqrtf(var + eps);
         b[e] = beta[c] - mean * a[e];
     }
@@ -524,18 +548,21 @@ int gn_finalize(float* partial_ws, float* sums, int ngroups, int nparts, hipStre
 }
 
 int gn_stats(const void* x, const void* x2, int C1, float* sums, float* partial_ws, int32_t n_img, int32_t S, int32_t C, int32_t frames_per_group,
-             void* stream_, float* amax_part = nullptr, bool finalize = true) {
+             void* stream_, float* amax_part = nullptr, bool finalize = true, bool pivot = false) {
     hipStream_t stream = (hipStream_t)stream_;
     GnGeom g;
-    if (!x || !sums || !partial_ws || !gn_geom(n_img, S, C, frames_per_group, g)) return VK_EINVAL;
+    if (!x || !sums || !partial_ws || !gn_geom(n_img, S, C, frames_per_group, g) || (pivot && amax_part)) return VK_EINVAL;
     dim3 grid(g.nchunks, n_img);
     const size_t lds_bytes = (size_t)2 * g.R * C * sizeof(float);
     if (amax_part)
-        hipLaunchKernelGGL(gn_stats_kernel<true>, grid, dim3(g.threads), lds_bytes, stream, (const uint16_t*)x, (const uint16_t*)x2, C1, partial_ws, S, C,
-                           g.CG, g.R, g.tok, amax_part);
+        hipLaunchKernelGGL((gn_stats_kernel<true, false>), grid, dim3(g.threads), lds_bytes, stream, (const uint16_t*)x, (const uint16_t*)x2, C1, partial_ws,
+                           S, C, g.CG, g.R, g.tok, amax_part, frames_per_group);
+    else if (pivot)   // (GN_PIVOT &&: the bf16 build instantiates no pivoted kernel)
+        hipLaunchKernelGGL((gn_stats_kernel<false, GN_PIVOT>), grid, dim3(g.threads), lds_bytes, stream, (const uint16_t*)x, (const uint16_t*)x2, C1, partial_ws,
+                           S, C, g.CG, g.R, g.tok, (float*)nullptr, frames_per_group);
     else
-        hipLaunchKernelGGL(gn_stats_kernel<false>, grid, dim3(g.threads), lds_bytes, stream, (const uint16_t*)x, (const uint16_t*)x2, C1, partial_ws, S, C,
-                           g.CG, g.R, g.tok, (float*)nullptr);
+        hipLaunchKernelGGL((gn_stats_kernel<false, false>), grid, dim3(g.threads), lds_bytes, stream, (const uint16_t*)x, (const uint16_t*)x2, C1, partial_ws,
+                           S, C, g.CG, g.R, g.tok, (float*)nullptr, frames_per_group);
     VK_CHECK_LAUNCH();
     if (!finalize) return VK_OK;   // (the apply pass folds the slots itself: gn_fold_parts)
     return gn_finalize(partial_ws, sums, g.ngroups, frames_per_group * g.nchunks, stream);
@@ -552,7 +579,7 @@ int gn_fold_parts(int32_t n_img, int32_t S, int32_t C, int32_t frames_per_group)
 
 // fold_nparts > 0: `sums` are the groups' stage-1 slots ([group][fold_nparts][64]) and the apply workgroups fold them themselves (no finalize launch)
 int gn_apply(const void* x, const void* x2, int C1, void* y, const float* gamma, const float* beta, const float* sums, int32_t n_img, int32_t S,
-             int32_t C, int32_t frames_per_group, float count, float eps, int32_t silu, void* stream_, int fold_nparts = 0) {
+             int32_t C, int32_t frames_per_group, float count, float eps, int32_t silu, void* stream_, int fold_nparts = 0, bool pivot = false) {
     hipStream_t stream = (hipStream_t)stream_;
     GnGeom g;
     if (!x || !y || !gamma || !beta || !sums || count <= 0.f || !gn_geom(n_img, S, C, frames_per_group, g)) return VK_EINVAL;
@@ -569,8 +596,10 @@ int gn_apply(const void* x, const void* x2, int C1, void* y, const float* gamma,
     static const int nt_env = [] { const char* e = getenv("VISTA_GN_NT"); return e ? atoi(e) & 3 : -1; }();
     const int nt_mode = nt_env >= 0 ? nt_env : ((long long)n_img * S * C * 2 >= (96LL << 20) ? 3 : 0);
     if (fold_nparts < 0 || fold_nparts > GN_FOLD_MAX) return VK_EINVAL;
-#define VK_GN_APPLY(NL, NS, FO) hipLaunchKernelGGL((gn_apply_kernel<NL, NS, FO>), grid, dim3(g.threads), 0, stream, (const uint16_t*)x, (const uint16_t*)x2, C1, (uint16_t*)y, \
-                                                   gamma, beta, sums, S, C, g.CG, g.R, frames_per_group, 1.f / count, eps, silu, tok_per_wg, fold_nparts)
+    if (pivot && (y == x || y == x2)) return VK_EINVAL;   // every workgroup of a group reads the pivot element of x: not in place
+#define VK_GN_APPLY_(NL, NS, FO, PV) hipLaunchKernelGGL((gn_apply_kernel<NL, NS, FO, PV>), grid, dim3(g.threads), 0, stream, (const uint16_t*)x, (const uint16_t*)x2, C1, \
+                                                       (uint16_t*)y, gamma, beta, sums, S, C, g.CG, g.R, frames_per_group, 1.f / count, eps, silu, tok_per_wg, fold_nparts)
+#define VK_GN_APPLY(NL, NS, FO) do { if (pivot) VK_GN_APPLY_(NL, NS, FO, GN_PIVOT); else VK_GN_APPLY_(NL, NS, FO, false); } while (0)
     if (fold_nparts > 0) {
         if (nt_mode == 3) VK_GN_APPLY(true, true, true);
         else if (nt_mode == 2) VK_GN_APPLY(false, true, true);
@@ -583,6 +612,7 @@ int gn_apply(const void* x, const void* x2, int C1, void* y, const float* gamma,
         else VK_GN_APPLY(false, false, false);
     }
 #undef VK_GN_APPLY
+#undef VK_GN_APPLY_
     VK_CHECK_LAUNCH();
     return VK_OK;
 }
@@ -624,10 +654,10 @@ extern "C" int vk_groupnorm_silu_cat_bf16(const void* x1, const void* x2, void* 
     const int C = C1 + C2;
     float* partial = stats_ws + (size_t)(n_img / frames_per_group) * 64;
     const int fold = gn_fold_parts(n_img, S, C, frames_per_group);
-    int rc = gn_stats(x1, x2, C1, stats_ws, partial, n_img, S, C, frames_per_group, stream_, nullptr, fold == 0);
+    int rc = gn_stats(x1, x2, C1, stats_ws, partial, n_img, S, C, frames_per_group, stream_, nullptr, fold == 0, GN_PIVOT);
     if (rc != VK_OK) return rc;
     const float count = (float)(C / 32) * (float)S * (float)frames_per_group;
-    return gn_apply(x1, x2, C1, y, gamma, beta, fold ? partial : stats_ws, n_img, S, C, frames_per_group, count, eps, silu, stream_, fold);
+    return gn_apply(x1, x2, C1, y, gamma, beta, fold ? partial : stats_ws, n_img, S, C, frames_per_group, count, eps, silu, stream_, fold, GN_PIVOT);
 }
 
 extern "C" int vk_groupnorm_silu_fp8(const void* x1, const void* x2, void* y8, float* scale_out, const float* gamma, const float* beta,
@@ -669,10 +699,10 @@ extern "C" int vk_groupnorm_silu_bf16(const void* x, void* y, const float* gamma
     // workspace: [n_img/fpg][64] sums, then [n_img][chunks][64] partial sums
     float* partial = stats_ws + (size_t)(n_img / frames_per_group) * 64;
     const int fold = gn_fold_parts(n_img, S, C, frames_per_group);
-    int rc = gn_stats(x, nullptr, 0, stats_ws, partial, n_img, S, C, frames_per_group, stream_, nullptr, fold == 0);
+    int rc = gn_stats(x, nullptr, 0, stats_ws, partial, n_img, S, C, frames_per_group, stream_, nullptr, fold == 0, GN_PIVOT);
     if (rc != VK_OK) return rc;
     const float count = (float)(C / 32) * (float)S * (float)frames_per_group;
-    return gn_apply(x, nullptr, 0, y, gamma, beta, fold ? partial : stats_ws, n_img, S, C, frames_per_group, count, eps, silu, stream_, fold);
+    return gn_apply(x, nullptr, 0, y, gamma, beta, fold ? partial : stats_ws, n_img, S, C, frames_per_group, count, eps, silu, stream_, fold, GN_PIVOT);
 }
 
 extern "C" int vk_layernorm_bf16(const void* x, void* y, void* sum_out, const float* gamma, const float* beta, const float* addvec,
