@@ -558,6 +558,100 @@ def test_splitk_conv3x3_and_temporal_conv():
     close(pt, reft, "plain temporal conv")
 
 
+# ------------------------------------------------------------------------------------------------ the GEMM-family kind table
+def _ln_ref(x, gamma, beta, eps=1e-5):
+    return F.layer_norm(x.float(), (x.shape[-1],), gamma, beta, eps)
+
+
+class _Norm:  # stands in for the LayerNorm parameter container
+    def __init__(self, C, seed=7):
+        g = torch.Generator().manual_seed(seed)
+        self.weight = (1 + 0.2 * torch.randn(C, generator=g)).cuda()
+        self.bias = (0.1 * torch.randn(C, generator=g)).cuda()
+        self.eps = 1e-5
+
+
+def _forced(ops, cfg, fn):
+    ops.TILE_CFG = cfg
+    try:
+        return fn()
+    finally:
+        ops.TILE_CFG = 0
+
+
+def _gemm_kind(ops, kind, n, H, W, C):
+    """One launch of the GEMM family -- a loader x an epilogue, named by kind -- on n images of H x W tokens with C channels: (fn, ref, N). fn(**kw)
+    launches it (kw: emit_stats=, out=), ref is torch fp32 on the same bf16 values, N the output width. rnd() seeds on the shape, so every test that
+    asks for a kind at a shape gets the same tensors."""
+    S = H * W
+    M = n * S
+    x = rnd(M, C)
+    x3 = x.view(n, S, C)
+    res = rnd(M, C, seed=3)
+    rv = rnd(n, C, seed=5).float()
+    if kind == "dense+res+stats":
+        w, b = rnd(C, C, scale=C ** -0.5, seed=1), rnd(C, seed=2).float()
+        pw = ops.pack_linear(w, b)
+        return (lambda **kw: ops.linear(x, pw, res1=res, rowvec=rv, rows_per_vec=S, emit_stats=True, **kw),
+                x.float() @ w.float().t() + b + res.float() + rv.repeat_interleave(S, 0), C)
+    if kind == "dense_strided_A":   # A is a column block of a wider tensor (lda = 3C): the last tile's buffer range ends inside the last row
+        xs = rnd(M, 3 * C, seed=11)[:, C:2 * C]
+        w, b = rnd(C, C, scale=C ** -0.5, seed=1), rnd(C, seed=2).float()
+        pw = ops.pack_linear(w, b)
+        return lambda **kw: ops.linear(xs, pw, res1=res, **kw), xs.float() @ w.float().t() + b + res.float(), C
+    if kind == "dense_K_32_mod_64":   # K = C + 64 is a multiple of 64 (the ABI's rule); an odd count of 64-deep steps = 2 (mod 4) 32-deep ones: both ring parities end the loop
+        xk = rnd(M, C + 64, seed=13)
+        w, b = rnd(C, C + 64, scale=C ** -0.5, seed=1), rnd(C, seed=2).float()
+        pw = ops.pack_linear(w, b)
+        return lambda **kw: ops.linear(xk, pw, **kw), xk.float() @ w.float().t() + b, C
+    if kind in ("dense_K4N+res+stats", "ff_out+blend"):   # (the caller asks for the first one's row sums: emit_stats=True)
+        h4 = rnd(M, 4 * C, seed=9)
+        w, b = rnd(C, 4 * C, scale=(4 * C) ** -0.5, seed=1), rnd(C, seed=2).float()
+        pw = ops.pack_linear(w, b)
+        if kind == "dense_K4N+res+stats":
+            return (lambda **kw: ops.linear(h4, pw, res1=res, rowvec=rv, rows_per_vec=S, **kw),
+                    h4.float() @ w.float().t() + b + res.float() + rv.repeat_interleave(S, 0), C)
+        return (lambda **kw: ops.linear(h4, pw, res1=res, alpha=0.4, res2=x, rowvec2=rv, beta=0.6, rows_per_vec=S, **kw),
+                0.4 * (h4.float() @ w.float().t() + b + res.float()) + 0.6 * (x.float() + rv.repeat_interleave(S, 0)), C)
+    if kind in ("qkv_lnfold", "geglu_lnfold"):
+        nrm = _Norm(C, 7)
+        Nw = 3 * C if kind == "qkv_lnfold" else 8 * C
+        w, b = rnd(Nw, C, scale=C ** -0.5, seed=1), rnd(Nw, seed=2).float()
+        pw = ops.pack_linear(w, b, ln=nrm) if kind == "qkv_lnfold" else ops.pack_geglu(w, b, ln=nrm)
+        st = ops.rowstats(x)
+        ref = _ln_ref(x, nrm.weight, nrm.bias) @ w.float().t() + b
+        if kind == "geglu_lnfold":
+            a, g = ref.chunk(2, dim=-1)
+            ref = a * F.gelu(g)
+        return lambda **kw: ops.linear(x, pw, ln=st, **kw), ref, ref.shape[1]
+    if kind.startswith("conv3x3"):
+        w, b = rnd(C, C, 3, 3, scale=(9 * C) ** -0.5, seed=1), rnd(C, seed=2).float()
+        pw = ops.pack_conv3x3(w, b)
+        xn = _tok2nchw(x3, n, H, W)
+        if kind == "conv3x3+emb+res":
+            return (lambda **kw: ops.conv3x3(x3, pw, n, H, W, rowvec=rv, res1=x3, **kw)[0],
+                    _nchw2tok(F.conv2d(xn, w.float(), b, padding=1)) + rv[:, None, :] + x3.float(), C)
+        if kind == "conv3x3_ups2":   # Upsample.forward: nearest x2, then conv (openaimodel.py:100-102), the upsample fused into the loader
+            return (lambda **kw: ops.conv3x3(x3, pw, n, H, W, ups=2, rowvec=rv, **kw)[0],
+                    _nchw2tok(F.conv2d(F.interpolate(xn, scale_factor=2, mode="nearest"), w.float(), b, padding=1)) + rv[:, None, :], C)
+        if kind == "conv3x3_stride2":
+            if H % 2 or W % 2:
+                pytest.skip("stride 2 needs even H, W")
+            return lambda **kw: ops.conv3x3(x3, pw, n, H, W, stride=2, **kw)[0], _nchw2tok(F.conv2d(xn, w.float(), b, stride=2, padding=1)), C
+        if H % 2 or W % 2:
+            pytest.skip("the asymmetric-pad Downsample needs even H, W")
+        return (lambda **kw: ops.conv3x3(x3, pw, n, H, W, stride=2, asym_pad=True, **kw)[0],
+                _nchw2tok(F.conv2d(F.pad(xn, (0, 1, 0, 1)), w.float(), b, stride=2)), C)
+    T = n   # conv_t3, conv_t3+blend: one clip of n frames
+    w, b = rnd(C, C, 3, 1, 1, scale=(3 * C) ** -0.5, seed=1), rnd(C, seed=2).float()
+    pw = ops.pack_conv_t3(w, b)
+    x5 = x3.float().view(1, T, S, 1, C).permute(0, 4, 1, 2, 3)
+    ref = F.conv3d(x5, w.float(), b, padding=(1, 0, 0)).permute(0, 2, 3, 4, 1).reshape(n, S, C)
+    if kind == "conv_t3":
+        return lambda **kw: ops.conv_t3(x3, pw, T, S, **kw), ref, C
+    return lambda **kw: ops.conv_t3(x3, pw, T, S, res2=x3, alpha=0.3, beta=1.0, **kw), 0.3 * ref + x3.float(), C
+
+
 # ------------------------------------------------------------------------------------------------ round 4: the pipelined 256x320 kernel
 @pytest.mark.parametrize("kind", ["dense+res+stats", "dense_strided_A", "qkv_lnfold", "ff_out+blend", "geglu_lnfold", "conv3x3+emb+res", "conv3x3_stride2",
                                   "conv3x3_asym", "conv3x3_ups2", "conv_t3", "conv_t3+blend"])
@@ -569,85 +663,8 @@ def test_gemm_pipe_is_bitwise_the_sixteen_wave_kernel(kind, n, H, W, C):
     openaimodel.py:198,232 (ResBlock convs), :136 (Downsample), model.py:77-81 (asymmetric pad), video_model.py:38-52 (time_stack),
     attention.py:85-110 (GEGLU / FeedForward), :344-346,421 (projections)."""
     ops = _ops()
-    S = H * W
-    M = n * S
-    x = rnd(M, C)
-    x3 = x.view(n, S, C)
-    res = rnd(M, C, seed=3)
-    rv = rnd(n, C, seed=5).float()
-    ref = None
-    if kind == "dense+res+stats":
-        w, b = rnd(C, C, scale=C ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_linear(w, b)
-        fn = lambda: ops.linear(x, pw, res1=res, rowvec=rv, rows_per_vec=S, emit_stats=True)  # noqa: E731
-        ref = x.float() @ w.float().t() + b + res.float() + rv.repeat_interleave(S, 0)
-    elif kind == "dense_strided_A":   # A is a column block of a wider tensor (lda = 3C): the last tile's buffer range ends inside the last row
-        wide = rnd(M, 3 * C, seed=11)
-        xs = wide[:, C:2 * C]
-        w, b = rnd(C, C, scale=C ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_linear(w, b)
-        fn = lambda: ops.linear(xs, pw, res1=res)  # noqa: E731
-        ref = xs.float() @ w.float().t() + b + res.float()
-    elif kind == "qkv_lnfold":
-        nrm = _Norm(C, 7)
-        w, b = rnd(3 * C, C, scale=C ** -0.5, seed=1), rnd(3 * C, seed=2).float()
-        pw = ops.pack_linear(w, b, ln=nrm)
-        st = ops.rowstats(x)
-        fn = lambda: ops.linear(x, pw, ln=st)  # noqa: E731
-        ref = _ln_ref(x, nrm.weight, nrm.bias) @ w.float().t() + b
-    elif kind == "ff_out+blend":
-        h4 = rnd(M, 4 * C, seed=9)
-        w, b = rnd(C, 4 * C, scale=(4 * C) ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_linear(w, b)
-        fn = lambda: ops.linear(h4, pw, res1=res, alpha=0.4, res2=x, rowvec2=rv, beta=0.6, rows_per_vec=S)  # noqa: E731
-        ref = 0.4 * (h4.float() @ w.float().t() + b + res.float()) + 0.6 * (x.float() + rv.repeat_interleave(S, 0))
-    elif kind == "geglu_lnfold":
-        nrm = _Norm(C, 7)
-        w, b = rnd(8 * C, C, scale=C ** -0.5, seed=1), rnd(8 * C, seed=2).float()
-        pw = ops.pack_geglu(w, b, ln=nrm)
-        st = ops.rowstats(x)
-        fn = lambda: ops.linear(x, pw, ln=st)  # noqa: E731
-        a, g = (_ln_ref(x, nrm.weight, nrm.bias) @ w.float().t() + b).chunk(2, dim=-1)
-        ref = a * F.gelu(g)
-    elif kind.startswith("conv3x3"):
-        w, b = rnd(C, C, 3, 3, scale=(9 * C) ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_conv3x3(w, b)
-        xn = _tok2nchw(x3, n, H, W)
-        if kind == "conv3x3+emb+res":
-            fn = lambda: ops.conv3x3(x3, pw, n, H, W, rowvec=rv, res1=x3)[0]  # noqa: E731
-            ref = _nchw2tok(F.conv2d(xn, w.float(), b, padding=1)) + rv[:, None, :] + x3.float()
-        elif kind == "conv3x3_ups2":   # Upsample.forward: nearest x2, then conv (openaimodel.py:100-102), the upsample fused into the loader
-            fn = lambda: ops.conv3x3(x3, pw, n, H, W, ups=2, rowvec=rv)[0]  # noqa: E731
-            ref = _nchw2tok(F.conv2d(F.interpolate(xn, scale_factor=2, mode="nearest"), w.float(), b, padding=1)) + rv[:, None, :]
-        elif kind == "conv3x3_stride2":
-            if H % 2 or W % 2:
-                pytest.skip("stride 2 needs even H, W")
-            fn = lambda: ops.conv3x3(x3, pw, n, H, W, stride=2)[0]  # noqa: E731
-            ref = _nchw2tok(F.conv2d(xn, w.float(), b, stride=2, padding=1))
-        else:
-            if H % 2 or W % 2:
-                pytest.skip("the asymmetric-pad Downsample needs even H, W")
-            fn = lambda: ops.conv3x3(x3, pw, n, H, W, stride=2, asym_pad=True)[0]  # noqa: E731
-            ref = _nchw2tok(F.conv2d(F.pad(xn, (0, 1, 0, 1)), w.float(), b, stride=2))
-    else:
-        T = n   # one clip of n frames
-        w, b = rnd(C, C, 3, 1, 1, scale=(3 * C) ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_conv_t3(w, b)
-        x5 = x3.float().view(1, T, S, 1, C).permute(0, 4, 1, 2, 3)
-        ref = F.conv3d(x5, w.float(), b, padding=(1, 0, 0)).permute(0, 2, 3, 4, 1).reshape(n, S, C)
-        if kind == "conv_t3":
-            fn = lambda: ops.conv_t3(x3, pw, T, S)  # noqa: E731
-        else:
-            fn = lambda: ops.conv_t3(x3, pw, T, S, res2=x3, alpha=0.3, beta=1.0)  # noqa: E731
-            ref = 0.3 * ref + x3.float()
-    outs = {}
-    for cfg in (7, 4):
-        ops.TILE_CFG = cfg
-        try:
-            outs[cfg] = fn()
-        finally:
-            ops.TILE_CFG = 0
-    o7, o4 = outs[7], outs[4]
+    fn, ref, _ = _gemm_kind(ops, kind, n, H, W, C)
+    o7, o4 = _forced(ops, 7, fn), _forced(ops, 4, fn)
     if isinstance(o7, tuple):
         (o7, s7), (o4, s4) = o7, o4
         assert s7.parts == s4.parts and torch.equal(s7.t, s4.t), "row-sum slabs differ"
@@ -664,58 +681,8 @@ def test_gemm_pipe2_is_bitwise_the_pipelined_kernel(kind, n, H, W, C):
     row-sum slabs, for every DENSE epilogue it takes, and against torch fp32. An A/B option of round 6 (off by default: profiles/r06_gemm_pipe2.txt).
     Reference call sites: attention.py:85-110 (GEGLU / FeedForward), :344-346,421 (projections)."""
     ops = _ops()
-    S = H * W
-    M = n * S
-    x = rnd(M, C)
-    res = rnd(M, C, seed=3)
-    rv = rnd(n, C, seed=5).float()
-    if kind == "dense+res+stats":
-        w, b = rnd(C, C, scale=C ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_linear(w, b)
-        fn = lambda: ops.linear(x, pw, res1=res, rowvec=rv, rows_per_vec=S, emit_stats=True)  # noqa: E731
-        ref = x.float() @ w.float().t() + b + res.float() + rv.repeat_interleave(S, 0)
-    elif kind == "dense_strided_A":
-        wide = rnd(M, 3 * C, seed=11)
-        xs = wide[:, C:2 * C]
-        w, b = rnd(C, C, scale=C ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_linear(w, b)
-        fn = lambda: ops.linear(xs, pw, res1=res)  # noqa: E731
-        ref = xs.float() @ w.float().t() + b + res.float()
-    elif kind == "dense_K_32_mod_64":   # K = C + 64 is a multiple of 64 (the ABI's rule); an odd count of 64-deep steps = 2 (mod 4) 32-deep ones: both ring parities end the loop
-        xk = rnd(M, C + 64, seed=13)
-        w, b = rnd(C, C + 64, scale=C ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_linear(w, b)
-        fn = lambda: ops.linear(xk, pw)  # noqa: E731
-        ref = xk.float() @ w.float().t() + b
-    elif kind == "qkv_lnfold":
-        nrm = _Norm(C, 7)
-        w, b = rnd(3 * C, C, scale=C ** -0.5, seed=1), rnd(3 * C, seed=2).float()
-        pw = ops.pack_linear(w, b, ln=nrm)
-        st = ops.rowstats(x)
-        fn = lambda: ops.linear(x, pw, ln=st)  # noqa: E731
-        ref = _ln_ref(x, nrm.weight, nrm.bias) @ w.float().t() + b
-    elif kind == "ff_out+blend":
-        h4 = rnd(M, 4 * C, seed=9)
-        w, b = rnd(C, 4 * C, scale=(4 * C) ** -0.5, seed=1), rnd(C, seed=2).float()
-        pw = ops.pack_linear(w, b)
-        fn = lambda: ops.linear(h4, pw, res1=res, alpha=0.4, res2=x, rowvec2=rv, beta=0.6, rows_per_vec=S)  # noqa: E731
-        ref = 0.4 * (h4.float() @ w.float().t() + b + res.float()) + 0.6 * (x.float() + rv.repeat_interleave(S, 0))
-    else:
-        nrm = _Norm(C, 7)
-        w, b = rnd(8 * C, C, scale=C ** -0.5, seed=1), rnd(8 * C, seed=2).float()
-        pw = ops.pack_geglu(w, b, ln=nrm)
-        st = ops.rowstats(x)
-        fn = lambda: ops.linear(x, pw, ln=st)  # noqa: E731
-        a, g = (_ln_ref(x, nrm.weight, nrm.bias) @ w.float().t() + b).chunk(2, dim=-1)
-        ref = a * F.gelu(g)
-    outs = {}
-    for cfg in (16, 7):
-        ops.TILE_CFG = cfg
-        try:
-            outs[cfg] = fn()
-        finally:
-            ops.TILE_CFG = 0
-    o2, o7 = outs[16], outs[7]
+    fn, ref, _ = _gemm_kind(ops, kind, n, H, W, C)
+    o2, o7 = _forced(ops, 16, fn), _forced(ops, 7, fn)
     if isinstance(o2, tuple):
         (o2, s2), (o7, s7) = o2, o7
         assert s2.parts == s7.parts and torch.equal(s2.t, s7.t), "row-sum slabs differ"
@@ -733,56 +700,17 @@ def test_gemm_tail_split_and_row_ranges_are_bitwise(kind, n, H, W):
     launch, (b) the forced single launch (tile_cfg 7 disables the split) and (c) three explicit row-range calls that together cover the rows
     must agree BIT FOR BIT -- outputs and row sums -- and match torch fp32. Reference call sites as test_gemm_pipe_is_bitwise_..."""
     ops = _ops()
-    Cc, S = 320, H * W
-    M = n * S
-    x = rnd(M, Cc)
-    x3 = x.view(n, S, Cc)
-    res = rnd(M, Cc, seed=3)
-    rv = rnd(n, Cc, seed=5).float()
-    if kind == "qkv_lnfold":
-        nrm = _Norm(Cc, 7)
-        w, b = rnd(3 * Cc, Cc, scale=Cc ** -0.5, seed=1), rnd(3 * Cc, seed=2).float()
-        pw = ops.pack_linear(w, b, ln=nrm)
-        st = ops.rowstats(x)
-        fn = lambda **kw: ops.linear(x, pw, ln=st, **kw)  # noqa: E731
-        ref = _ln_ref(x, nrm.weight, nrm.bias) @ w.float().t() + b
-        N = 3 * Cc
-    elif kind == "dense_K4N+res+stats":
-        h4 = rnd(M, 4 * Cc, seed=9)
-        w, b = rnd(Cc, 4 * Cc, scale=(4 * Cc) ** -0.5, seed=1), rnd(Cc, seed=2).float()
-        pw = ops.pack_linear(w, b)
-        fn = lambda **kw: ops.linear(h4, pw, res1=res, rowvec=rv, rows_per_vec=S, **kw)  # noqa: E731
-        ref = h4.float() @ w.float().t() + b + res.float() + rv.repeat_interleave(S, 0)
-        N = Cc
-    elif kind == "conv3x3+emb+res":
-        w, b = rnd(Cc, Cc, 3, 3, scale=(9 * Cc) ** -0.5, seed=1), rnd(Cc, seed=2).float()
-        pw = ops.pack_conv3x3(w, b)
-        fn = lambda **kw: ops.conv3x3(x3, pw, n, H, W, rowvec=rv, res1=x3, **kw)[0]  # noqa: E731
-        ref = (_nchw2tok(F.conv2d(_tok2nchw(x3, n, H, W), w.float(), b, padding=1)) + rv[:, None, :] + x3.float()).reshape(M, Cc)
-        N = Cc
-    else:
-        w, b = rnd(Cc, Cc, 3, 1, 1, scale=(3 * Cc) ** -0.5, seed=1), rnd(Cc, seed=2).float()
-        pw = ops.pack_conv_t3(w, b)
-        x5 = x3.float().view(1, n, S, 1, Cc).permute(0, 4, 1, 2, 3)
-        ref = (0.3 * F.conv3d(x5, w.float(), b, padding=(1, 0, 0)).permute(0, 2, 3, 4, 1).reshape(n, S, Cc) + x3.float()).reshape(M, Cc)
-        fn = lambda **kw: ops.conv_t3(x3, pw, n, S, res2=x3, alpha=0.3, beta=1.0, **kw)  # noqa: E731
-        N = Cc
+    M = n * H * W
+    fn, ref, N = _gemm_kind(ops, kind, n, H, W, 320)
     stats = kind == "dense_K4N+res+stats"
-    ops.TILE_CFG = 64   # the launcher's own choice + the tail-split rule (an A/B option, measured without gain and off by default)
-    try:
-        auto = fn(emit_stats=True) if stats else fn()
-    finally:
-        ops.TILE_CFG = 0
-    ops.TILE_CFG = 7
-    try:
-        single = fn(emit_stats=True) if stats else fn()
-    finally:
-        ops.TILE_CFG = 0
+    kw = {"emit_stats": True} if stats else {}
+    auto = _forced(ops, 64, lambda: fn(**kw))   # the launcher's own choice + the tail-split rule (an A/B option, measured without gain and off by default)
+    single = _forced(ops, 7, lambda: fn(**kw))
     if stats:
         (auto, sa), (single, ss) = auto, single
         assert sa.parts == ss.parts and torch.equal(sa.t, ss.t), "row-sum slabs of the split launch differ from the single launch"
         _check_stats(sa, auto)
-    close(auto.reshape(M, N), ref, f"tail split {kind}")
+    close(auto.reshape(M, N), ref.reshape(M, N), f"tail split {kind}")
     assert torch.equal(auto, single), "split and single launches must agree bit for bit"
     # the shape is one the rule splits: at least one full round and a last round filled to <= 40 %
     tiles_n, tiles_m = N // 320, (M + 255) // 256
@@ -842,17 +770,6 @@ def test_gemm_pipe_is_what_the_launcher_runs_and_refusals():
 
 # ------------------------------------------------------------------------------------------------ round 2: folded LayerNorm, row sums,
 # two-source (concat) loaders, rowvec2
-def _ln_ref(x, gamma, beta, eps=1e-5):
-    return F.layer_norm(x.float(), (x.shape[-1],), gamma, beta, eps)
-
-
-class _Norm:  # stands in for the LayerNorm parameter container
-    def __init__(self, C, seed):
-        self.weight = (1.0 + 0.2 * torch.randn(C, generator=torch.Generator().manual_seed(seed))).cuda()
-        self.bias = (0.3 * torch.randn(C, generator=torch.Generator().manual_seed(seed + 1))).cuda()
-        self.eps = 1e-5
-
-
 def _check_stats(st, out):
     """RowStats slabs summed over parts == (sum, sum of squares) of the bf16 output rows."""
     o = out.float()
@@ -1077,14 +994,6 @@ def test_packed_weights_follow_parameter_versions():
 
 
 # ------------------------------------------------------------------------------------------------ fused FeedForward (level 0)
-class _Norm:
-    def __init__(self, C, seed=7):
-        g = torch.Generator().manual_seed(seed)
-        self.weight = (1 + 0.2 * torch.randn(C, generator=g)).cuda()
-        self.bias = (0.1 * torch.randn(C, generator=g)).cuda()
-        self.eps = 1e-5
-
-
 def _ff_reference(x, w1, b1, w2, b2, norm):
     """FeedForward.net = [GEGLU, Dropout, Linear] (vwm/modules/attention.py:85-128) in fp32, with the hidden activation rounded to bf16
     where both kernel forms round it."""
