@@ -420,6 +420,39 @@ int vk_ensemble_frame_stats(const float* x, double* frame_sum, float* map, doubl
 int vk_heat_overlay_u8(const float* frames, const float* map, void* out, int32_t n_img, int32_t H, int32_t W, int32_t cell, float inv_vmax,
                        float alpha, void* stream);
 
+/* ------------------------------------------------------------------ evaluation front door (csrc/fidelity.hip)
+ * Added under ABI v9 without a version step, as the reward entry points were: purely additive. Storage-type independent: the same code is
+ * linked into both libraries.
+ *
+ * vk_frame_fidelity_u8: how close the 8-bit frames `a` are to the 8-bit frames `b` -- the bytes vk_frames_to_u8 writes, so a number about them is
+ * a number about the saved pictures. a, b (n, H, W, 3) uint8, dense. Per frame f and channel c:
+ *   sse[f][c]      uint64: sum over the frame of (a - b)^2. An exact integer: any order gives it.
+ *   ssim_sum[f][c] fp64: sum of the SSIM index (Wang, Bovik, Sheikh, Simoncelli 2004) over the (H - 10) * (W - 10) positions at which the 11 x 11
+ *                  window lies inside the frame (no padding); the caller divides. Per window, in fp32: the weighted moments under the separable
+ *                  window w (rows, then columns) of x' = a - 128, y' = b - 128 (exact in fp32; the pivot keeps the variances of bright, flat
+ *                  regions out of the cancellation of two numbers near 255^2), mx, my, xx, yy, xy, and
+ *                      ((2 ux uy + C1) (2 sxy + C2)) / ((ux^2 + uy^2 + C1) (sxx + syy + C2)),   ux = mx + 128, uy = my + 128,
+ *                      sxx = xx - mx^2, syy = yy - my^2, sxy = xy - mx my,   C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2
+ *                  with the index expression kept free of FMA contraction, so that a frame scored against itself gives exactly 1 per window.
+ *   window11       VK_FIDELITY_TAPS fp32 weights in HOST memory, read during the call (they reach the kernel by value): the caller's Gaussian
+ *                  (sigma 1.5, normalised in float64, rounded once).
+ *   ws             n * vk_frame_fidelity_ws_bytes(H, W) bytes of scratch, the caller's, 8-byte aligned: one fp64 and one uint64 partial per
+ *                  workgroup and channel. A workgroup owns a VK_FIDELITY_TILE_H x VK_FIDELITY_TILE_W tile of window positions of one frame (and
+ *                  the squared differences of its pixels; the last tile of an axis those up to the frame's edge); a fold pass adds a frame's
+ *                  partials in a fixed order. Which workgroup owns what is a function of (H, W) alone: no atomics, bitwise repeatable, and a
+ *                  frame's values do not change with n or with the frames around it.
+ *   Where W % 4 == 0 the halo is loaded 4 bytes per lane: a and b must then be 4-byte aligned; any other W takes any alignment.
+ *   The entry point allocates nothing and synchronises nothing. Not built here: any perceptual metric that needs a pretrained network.
+ *   VK_EINVAL: a NULL pointer, n <= 0, n > 65535, H < 11 or W < 11, ws / sse / ssim_sum not 8-byte aligned, a or b misaligned where W % 4 == 0,
+ *   a frame of more tiles than vk_frame_fidelity_ws_bytes can state.
+ * vk_frame_fidelity_ws_bytes: the workspace bytes PER FRAME for (H, W) frames, or VK_EINVAL (H < 11, W < 11, more than 2^31 - 1 bytes). */
+#define VK_FIDELITY_TAPS 11
+#define VK_FIDELITY_TILE_H 16
+#define VK_FIDELITY_TILE_W 32
+int vk_frame_fidelity_ws_bytes(int32_t H, int32_t W);
+int vk_frame_fidelity_u8(const void* a, const void* b, uint64_t* sse, double* ssim_sum, void* ws, const float* window11 /* HOST memory */,
+                         int32_t n, int32_t H, int32_t W, void* stream);
+
 /* ------------------------------------------------------------------ exchange packing of the frame-sharded step (ABI v9; csrc/reshard.hip)
  * Storage-type independent: the same code is linked into both libraries.
  *

@@ -125,6 +125,8 @@ SIGNATURES = {
     "vk_frames_to_u8": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "vk_ensemble_frame_stats": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "vk_heat_overlay_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp],
+    "vk_frame_fidelity_ws_bytes": [_i32, _i32],
+    "vk_frame_fidelity_u8": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _vp],
     "vk_copy_row_boxes": [_vp, _vp, C.POINTER(VkRowBoxes), _i64, _i64, _i32, _vp],
     "vk_abi_version": [],
     "vk_act_dtype": [],

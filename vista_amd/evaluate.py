@@ -1,0 +1,301 @@
+"""`python -m vista_amd.evaluate`: sample scenes as `vista_amd.sample` does and score every predicted frame against the real one.
+
+Every flag of `vista_amd.sample` under its name with its default (the parser is built from sample.parse_args); on top: --n_scenes (how many
+scenes to score; 0 = to the end of the dataset, for the sequential walk only), --no_pictures (write the metrics files only) and --compare DIR
+(score the pictures an earlier run wrote under DIR; no model is built).
+
+    python -m vista_amd.evaluate --ckpt ckpts/vista.safetensors --action traj --rand_gen --n_scenes 50 --save outputs
+    python -m vista_amd.evaluate --compare outputs --n_conds 1
+
+Per scene: sample.run with the sampling CLI's seeding, ops.frames_to_u8 on both stacks (the bytes of the saved pictures), PSNR and SSIM from
+vk_frame_fidelity_u8 (vista_amd/fidelity.py). A rollout predicts n_rounds * (n_frames - 3) + 3 frames while the sampler loads n_frames: where
+the scene's annotation lists more, the additional real frames are loaded here at the same size, and as many frames are scored as have ground
+truth. One JSON line per scene goes to <save>/metrics.jsonl, the means over scenes and the horizon curve (mean PSNR / SSIM at each frame index)
+to <save>/metrics_summary.json; both files describe this run only. The first --n_conds frames are conditioning frames: listed, and excluded from
+every mean. A mean over frames of which one is identical to its ground truth (infinite PSNR) is infinite, and written as null.
+
+Not built: the IMG dataset (one picture repeated has no future to compare against) and several GPUs (WORLD_SIZE > 1) are refused by name; the
+natural multi-GPU form is scene i on rank i mod W with a merge of the records. Perceptual metrics that need a pretrained network are not built.
+"""
+import json
+import math
+import os
+import random
+import re
+import sys
+import time
+
+from . import config, fidelity, sample
+from ._lib import VistaHipError
+from . import sample_utils as SU
+
+PICTURE_NAME = re.compile(r"^(?P<dataset>.+)_(?P<index>\d{6})_(?P<frame>\d{4})\.png$")   # perform_save_locally's image names
+
+
+def parse_args(**parser_kwargs):
+    parser = sample.parse_args(**parser_kwargs)
+    add = parser.add_argument
+    add("--n_scenes", type=int, default=0, help="number of scenes to score (0: to the end of the dataset; needs the sequential walk, --rand_gen)")
+    add("--no_pictures", action="store_true", help="write metrics.jsonl and metrics_summary.json only, no pictures")
+    add("--compare", type=str, default=None, metavar="DIR",
+        help="score DIR/virtual/images against DIR/real/images (an earlier run's pictures) and write the metrics files into DIR; no model is built")
+    return parser
+
+
+def check_run(opt, net_params=None):
+    """Refuses, by name and before any model is built, what an evaluation run cannot do."""
+    SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, net_params)
+    if opt.height < fidelity.TAPS or opt.width < fidelity.TAPS:
+        raise ValueError(f"--height {opt.height} --width {opt.width}: SSIM takes an {fidelity.TAPS} x {fidelity.TAPS} window")
+    if opt.dataset == "IMG":
+        raise ValueError("--dataset IMG: one picture repeated has no future frames to score a prediction against; evaluate needs a dataset "
+                         "of annotated scenes (NUSCENES)")
+    if opt.n_scenes < 0:
+        raise ValueError(f"--n_scenes {opt.n_scenes}: a count of scenes, or 0 for the whole dataset")
+    if opt.n_scenes == 0 and opt.rand_gen:
+        raise ValueError("--n_scenes 0 (to the end of the dataset) with the random walk: the reference's random walk never ends by itself; "
+                         "give --n_scenes N, or --rand_gen for the sequential walk")
+
+
+def check_world():
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError(f"WORLD_SIZE {os.environ['WORLD_SIZE']}: vista_amd.evaluate runs on one GPU (scene-per-rank evaluation with a merge of "
+                         "the records is not built); start it without torch.distributed.run")
+
+
+def rollout_length(n_frames, n_rounds):
+    return n_rounds * (n_frames - 3) + 3 if n_rounds > 1 else n_frames
+
+
+def future_frames(index, n_frames, upto, dataset="NUSCENES", data_root=None, anno_file=None):
+    """The paths of the scene's real frames n_frames .. upto - 1, as far as its annotation lists them and the files exist."""
+    src = SU.DATASET2SOURCES[dataset]
+    data_root = src["data_root"] if data_root is None else data_root
+    anno_file = src["anno_file"] if anno_file is None else anno_file
+    with open(anno_file, "r") as f:
+        scenes = json.load(f)
+    names = scenes[index % len(scenes)]["frames"][n_frames:upto]
+    paths = []
+    for name in names:
+        path = os.path.join(data_root, name)
+        if not os.path.exists(path):
+            break
+        paths.append(path)
+    return paths
+
+
+# ---- records ------------------------------------------------------------------------------------------------------------------------------
+def _num(v):
+    """A float for JSON: None where it is not finite (an infinite PSNR, a mean over nothing)."""
+    v = float(v)
+    return v if math.isfinite(v) else None
+
+
+def _mean(values):
+    """The mean of a list of floats in float64, in list order; nan for an empty list."""
+    return math.fsum(values) / len(values) if values else float("nan")
+
+
+def frame_round(i, n_frames):
+    """The sampling round that produced frame i of a rollout: the first window holds n_frames, every later one adds n_frames - 3."""
+    return 0 if i < n_frames else 1 + (i - n_frames) // (n_frames - 3)
+
+
+def make_record(index, frame_list, report, *, seed, action, n_conds, n_rounds, n_frames, timings=None):
+    """The JSON record of one scene from its FidelityReport (one entry per scored frame)."""
+    scored = len(report.psnr)
+    psnr, ssim = [float(v) for v in report.psnr], [float(v) for v in report.ssim]
+    cond = [i for i in range(scored) if i < n_conds]
+    pred = [i for i in range(scored) if i >= n_conds]
+    rounds = []
+    for r in range(max(1, n_rounds)):
+        members = [i for i in pred if frame_round(i, n_frames) == r]
+        if members:
+            rounds.append({"round": r, "frames": len(members), "mean_psnr": _num(_mean([psnr[i] for i in members])),
+                           "mean_ssim": _num(_mean([ssim[i] for i in members]))})
+    return {"index": int(index), "frames": [frame_list[0]], "seed": int(seed), "action": str(action), "n_conds": int(n_conds),
+            "n_rounds": int(n_rounds), "frames_scored": scored,
+            "psnr": [_num(v) for v in psnr], "ssim": [_num(v) for v in ssim], "sse": [[int(c) for c in row] for row in report.sse],
+            "cond": cond, "mean_psnr": _num(_mean([psnr[i] for i in pred])), "mean_ssim": _num(_mean([ssim[i] for i in pred])),
+            "rounds": rounds, "timings": {k: round(float(v), 4) for k, v in (timings or {}).items()}}
+
+
+def start_records(save_dir):
+    """An empty <save_dir>/metrics.jsonl: the file describes one run, as the summary does. Returns its path."""
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, "metrics.jsonl")
+    open(path, "w").close()
+    return path
+
+
+def append_record(save_dir, record):
+    """One line per scene at the end of <save_dir>/metrics.jsonl. Returns the file's path."""
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, "metrics.jsonl")
+    with open(path, "a") as f:
+        f.write(json.dumps(record, allow_nan=False) + "\n")
+    return path
+
+
+def summarize(records):
+    """Means over scenes and the horizon curve: at each frame index the mean PSNR and SSIM over the scenes that scored that index as a predicted
+    (not a conditioning) frame. null where no scene did, or where a PSNR in the mean is infinite (written as null in the record)."""
+    def scene_mean(key):
+        vals = [r[key] for r in records if r["frames_scored"] > len(r["cond"])]
+        return None if not vals or any(v is None for v in vals) else _num(_mean(vals))
+    length = max((r["frames_scored"] for r in records), default=0)
+    horizon = {"frame": list(range(length)), "scenes": [], "psnr": [], "ssim": []}
+    for i in range(length):
+        has = [r for r in records if i < r["frames_scored"] and i not in r["cond"]]
+        horizon["scenes"].append(len(has))
+        for key in ("psnr", "ssim"):
+            vals = [r[key][i] for r in has]
+            horizon[key].append(None if not vals or any(v is None for v in vals) else _num(_mean(vals)))
+    return {"scenes": len(records), "mean_psnr": scene_mean("mean_psnr"), "mean_ssim": scene_mean("mean_ssim"), "horizon": horizon}
+
+
+def write_summary(save_dir, records):
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, "metrics_summary.json")
+    with open(path, "w") as f:
+        json.dump(summarize(records), f, allow_nan=False, indent=1)
+        f.write("\n")
+    return path
+
+
+# ---- offline: the pictures of an earlier run ----------------------------------------------------------------------------------------------------
+def picture_pairs(directory):
+    """DIR/virtual/images and DIR/real/images -> [(dataset, index, [(frame, virtual path, real path)])], scenes and frames in ascending order:
+    the pictures both sides hold under the reference's names <dataset>_<index:06>_<frame:04>.png."""
+    sides = []
+    for sub in ("virtual", "real"):
+        folder = os.path.join(directory, sub, "images")
+        if not os.path.isdir(folder):
+            raise FileNotFoundError(f"--compare {directory}: {folder} does not exist (a run without --no_pictures writes it)")
+        sides.append({n: os.path.join(folder, n) for n in os.listdir(folder) if PICTURE_NAME.match(n)})
+    scenes = {}
+    for name in sorted(set(sides[0]) & set(sides[1])):
+        m = PICTURE_NAME.match(name)
+        scenes.setdefault((m["dataset"], int(m["index"])), []).append((int(m["frame"]), sides[0][name], sides[1][name]))
+    if not scenes:
+        raise FileNotFoundError(f"--compare {directory}: no picture occurs under both virtual/images and real/images")
+    return [(d, i, sorted(frames)) for (d, i), frames in sorted(scenes.items())]
+
+
+def compare(opt):
+    """--compare DIR: the same records and summary from the saved pictures. The bytes are the ones the online run scored, so are the numbers."""
+    import numpy as np
+    import torch
+    from PIL import Image
+    check_world()
+    if not 1 <= opt.n_conds:
+        raise ValueError(f"--n_conds {opt.n_conds}: at least one conditioning frame")
+    scenes = picture_pairs(opt.compare)
+    if not torch.cuda.is_available():
+        raise VistaHipError("evaluate --compare: no GPU is visible; vista_amd runs on the MI355X only (no CPU / eager fallback)")
+    start_records(opt.compare)
+    records = []
+    for dataset, index, frames in scenes:
+        t0 = time.perf_counter()
+        stacks = []
+        for side in (1, 2):
+            pictures = []
+            for entry in frames:
+                with Image.open(entry[side]) as im:
+                    pictures.append(np.array(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8))
+            if len({p.shape for p in pictures}) != 1:
+                raise ValueError(f"--compare {opt.compare}: the pictures of {dataset}_{index:06} differ in size")
+            stacks.append(torch.from_numpy(np.stack(pictures)).cuda())
+        t1 = time.perf_counter()
+        report = fidelity.frame_metrics(stacks[0], stacks[1])
+        timings = {"load": t1 - t0, "metrics": time.perf_counter() - t1}
+        record = make_record(index, [frames[0][2]], report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
+                             n_frames=opt.n_frames, timings=timings)
+        append_record(opt.compare, record)
+        records.append(record)
+        print(_scene_line(record), flush=True)
+    write_summary(opt.compare, records)
+    return 0
+
+
+def _scene_line(record):
+    shown = ", ".join(f"{k} " + ("null" if record[k] is None else f"{record[k]:.4f}") for k in ("mean_psnr", "mean_ssim"))
+    return (f"evaluate {record['index']}: {record['frames_scored']} frames, {shown} | "
+            + ", ".join(f"{k} {v:.2f} s" for k, v in record["timings"].items()))
+
+
+# ---- online ---------------------------------------------------------------------------------------------------------------------------------
+def main(argv=None):
+    opt, _unknown = parse_args(prog="python -m vista_amd.evaluate").parse_known_args(argv)
+    if opt.compare is not None:
+        return compare(opt)
+    # what cannot run is refused here, before 2.5 billion parameters are built
+    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
+    check_run(opt, net_params)
+    check_world()
+    return _evaluate_loop(opt)
+
+
+def _evaluate_loop(opt):
+    """The loop of vista_amd.sample with the metrics stage behind every scene."""
+    import torch
+    if opt.low_vram:
+        print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
+    spec = dict(SU.VERSION2SPECS[opt.version])
+    if opt.config:
+        spec["config"] = opt.config
+    if opt.ckpt:
+        spec["ckpt"] = opt.ckpt
+    model = SU.init_model(spec)
+    virtual_path, real_path = os.path.join(opt.save, "virtual"), os.path.join(opt.save, "real")
+    start_records(opt.save)
+    records = []
+
+    sample_index = 0
+    while sample_index >= 0:
+        sample.seed_everything(opt.seed)
+        frame_list, sample_index, dataset_length, action_dict = SU.get_sample(sample_index, opt.dataset, opt.n_frames, opt.action,
+                                                                              data_root=opt.data_root, anno_file=opt.anno_file)
+        timings = {}
+        samples, _samples_z, inputs = sample.run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames,
+                                                 n_rounds=opt.n_rounds, n_conds=opt.n_conds, n_steps=opt.n_steps, cfg_scale=opt.cfg_scale,
+                                                 cond_aug=opt.cond_aug, eager=opt.eager, timings=timings)
+        # ground truth beyond the sampler's window: the scene's own later frames, as far as the annotation lists them
+        t0 = time.perf_counter()
+        real = inputs
+        if samples.shape[0] > inputs.shape[0]:
+            more = future_frames(sample_index, opt.n_frames, samples.shape[0], opt.dataset, opt.data_root, opt.anno_file)
+            if more:
+                real = torch.cat([inputs, SU.load_img_seq(more, opt.height, opt.width, "cuda")])
+        scored = min(samples.shape[0], real.shape[0])
+        torch.cuda.synchronize()
+        timings["load"] = timings.get("load", 0.0) + time.perf_counter() - t0
+        t0 = time.perf_counter()
+        report = fidelity.frame_metrics(samples[:scored].float(), real[:scored].float())   # (its copy to the host ends the stage)
+        timings["metrics"] = time.perf_counter() - t0
+        if not opt.no_pictures:
+            t0 = time.perf_counter()
+            for path, frames in ((virtual_path, samples), (real_path, real)):
+                for mode in ("videos", "grids", "images"):
+                    SU.perform_save_locally(path, frames, mode, opt.dataset, sample_index)
+            timings["save"] = time.perf_counter() - t0
+        record = make_record(sample_index, frame_list, report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
+                             n_frames=opt.n_frames, timings=timings)
+        append_record(opt.save, record)
+        records.append(record)
+        print(_scene_line(record), flush=True)
+
+        if opt.n_scenes and len(records) >= opt.n_scenes:
+            break
+        if opt.rand_gen:
+            sample_index += random.randint(1, max(1, dataset_length - 1))
+        else:
+            sample_index += 1
+            if dataset_length <= sample_index:
+                sample_index = -1
+    write_summary(opt.save, records)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

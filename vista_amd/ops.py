@@ -1330,6 +1330,38 @@ def heat_overlay_u8(frames, fmap, vmax, alpha=0.6):
     return out
 
 
+# ---- evaluation front door (csrc/fidelity.hip) ----
+FIDELITY_TAPS, FIDELITY_TILE_H, FIDELITY_TILE_W = 11, 16, 32   # VK_FIDELITY_* of include/vista_hip.h
+
+
+def frame_fidelity_u8(a, b):
+    """a, b (n, H, W, 3) uint8, dense, on the GPU (the bytes frames_to_u8 writes) -> (sse (n, 3) int64, ssim_sum (n, 3) float64): per frame and
+    channel the exact sum of squared differences and the sum of the SSIM index over the (H - 10) * (W - 10) valid window positions
+    (vk_frame_fidelity_u8; window: fidelity.WINDOW_F32, fixed-order fp64 reduction). Nothing is synchronised: both results stay on the GPU."""
+    from . import fidelity
+    _need(a, torch.uint8, "a")
+    _need(b, torch.uint8, "b")
+    if a.dim() != 4 or a.shape[3] != 3 or a.shape != b.shape:
+        raise ValueError(f"frame_fidelity_u8: expected two (n, H, W, 3) uint8 stacks of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.device != b.device:
+        raise ValueError(f"frame_fidelity_u8: a is on {a.device}, b is on {b.device}")
+    if not (a.is_contiguous() and b.is_contiguous()):
+        raise ValueError("frame_fidelity_u8: a and b must be dense (contiguous) stacks")
+    n, H, W, _ = a.shape
+    if W % 4 == 0:   # the kernel loads 4 bytes per lane there (a dense view into another tensor's storage may start anywhere)
+        a = a if a.data_ptr() % 4 == 0 else a.clone()
+        b = b if b.data_ptr() % 4 == 0 else b.clone()
+    lib = _lib.load()
+    per_frame = lib.vk_frame_fidelity_ws_bytes(H, W)
+    check(min(per_frame, 0), "vk_frame_fidelity_ws_bytes")
+    sse = torch.empty((max(n, 1), 3), dtype=torch.int64, device=a.device)[:n]
+    ssim_sum = torch.empty((max(n, 1), 3), dtype=torch.float64, device=a.device)[:n]
+    ws = torch.empty(max(n, 1) * per_frame // 8, dtype=torch.float64, device=a.device)
+    check(lib.vk_frame_fidelity_u8(_p(a), _p(b), _p(sse), _p(ssim_sum), _p(ws), fidelity.window_ptr(), n, H, W, _stream()),
+          "vk_frame_fidelity_u8")
+    return sse, ssim_sum
+
+
 # ---- exchange packing of the frame-sharded step (csrc/reshard.hip, ABI v9) ----
 def row_boxes(boxes):
     """A list of (src_row, dst_row, src_stride_b, src_stride_t, dst_stride_b, dst_stride_t, nb, nt, ns) tuples -> the VkRowBoxes the library
