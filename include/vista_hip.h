@@ -483,6 +483,65 @@ typedef struct VkRowBoxes {
 int vk_copy_row_boxes(const void* src, void* dst, const VkRowBoxes* boxes /* HOST memory */, int64_t src_rows, int64_t dst_rows,
                       int32_t row_bytes, void* stream);
 
+/* ------------------------------------------------------------------ drive front door (csrc/overlay.hip)
+ * Added under ABI v9 without a version step, as the reward and evaluation entry points were: purely additive. Storage-type independent: the
+ * same code is linked into both libraries.
+ *
+ * vk_stroke_overlay_u8: anti-aliased strokes (round-capped line segments and discs) drawn over 8-bit frames -- the head-up display of a steered
+ * rollout. in, out (n, H, W, 3) uint8, dense; out may be in (every byte is read and written by the same thread).
+ *   A plan is up to VK_OVERLAY_MAX_SETS stroke sets over up to VK_OVERLAY_MAX_STROKES strokes over up to VK_OVERLAY_MAX_SEGMENTS segments. A set
+ *   is the run [stroke_begin, stroke_begin + stroke_count) of strokes, a stroke a colour K (per channel, in [0, 255]), an alpha in [0, 1], a
+ *   half-width r >= 0 and the run [seg_begin, seg_begin + seg_count) of segments; a segment is a = (ax, ay), b = (bx, by) in pixel coordinates
+ *   (x to the right, y down, the first pixel's centre at (0.5, 0.5)) and inv_len2 = 1 / |b - a|^2, formed by the caller in fp32. A disc is a
+ *   segment with a == b and inv_len2 = 0. Runs may overlap and may be empty.
+ *   set_of_frame [n] int32 in DEVICE memory: frame i is drawn with set set_of_frame[i]; a value outside [0, n_sets) (-1 by convention) copies
+ *   the frame. One launch draws a whole video whose rounds carry different commands.
+ *   Per pixel centre p = (x + 0.5, y + 0.5), in fp32, every operation rounded once and nothing contracted into an FMA:
+ *     d    = b - a
+ *     t    = clamp(((p.x - a.x) * d.x + (p.y - a.y) * d.y) * inv_len2, 0, 1)          (no division on the device)
+ *     q    = a + t * d,   e = p - q,   dist = sqrt(e.x * e.x + e.y * e.y)             (correctly rounded square root)
+ *     cov  = clamp((r + 0.5) - dist, 0, 1)
+ *   A stroke's coverage is the MAXIMUM of cov over its segments: exact and order-free, so the joints of a polyline are not blended twice.
+ *   The strokes of a set composite in list order, per channel:  f <- f + (alpha * cov) * (K - f), starting from f = float(byte); the final
+ *   cast truncates. The bytes equal a numpy float32 evaluation of this text (tests/_overlay_ref.py).
+ *   A pixel with cov = 0 keeps f exactly, so what lies outside a stroke's bounding box (its segments' extent grown by r + 0.5 and a margin of
+ *   two pixels for the rounding of q and dist) is skipped: a workgroup owns a VK_OVERLAY_TILE_H x VK_OVERLAY_TILE_W tile of one frame and tests
+ *   the boxes of its frame's set and strokes with wave-uniform (scalar) comparisons; a tile no box touches is a plain copy, or nothing at all
+ *   where out == in.
+ *   Plan passing: `plan` is HOST memory, read during the call; it reaches the kernel by value in its argument, where every field is fetched by
+ *   scalar loads. The maxima keep that argument under 3 KiB of the 4 KiB a kernel argument may take (8 sets x 24 + 32 strokes x 44 + 64
+ *   segments x 20 bytes in the kernel's own layout); a caller with more splits the frames over several calls. The entry point allocates
+ *   nothing and synchronises nothing.
+ *   Rows are 3 W bytes: where W % 4 == 0 a lane moves its four pixels as three dwords (in and out must then be 4-byte aligned), any other W is
+ *   moved byte by byte and takes any alignment. The path is a function of W alone.
+ *   VK_EINVAL (before any launch): a NULL in / out / set_of_frame / plan, set_of_frame not 4-byte aligned, in or out misaligned where
+ *   W % 4 == 0, n / H / W <= 0, n > 65535, a count below 0 or above its maximum, a run that leaves its table, an alpha outside [0, 1], a
+ *   colour outside [0, 255], a negative or non-finite r or inv_len2, a coordinate or r that is not finite or beyond 2^20 in magnitude. */
+#define VK_OVERLAY_MAX_SETS 8
+#define VK_OVERLAY_MAX_STROKES 32
+#define VK_OVERLAY_MAX_SEGMENTS 64
+#define VK_OVERLAY_TILE_H 16
+#define VK_OVERLAY_TILE_W 64
+typedef struct VkStrokeSegment {
+    float ax, ay, bx, by, inv_len2;
+} VkStrokeSegment;
+typedef struct VkStroke {
+    float color[3];
+    float alpha, r;
+    int32_t seg_begin, seg_count;
+} VkStroke;
+typedef struct VkStrokeSet {
+    int32_t stroke_begin, stroke_count;
+} VkStrokeSet;
+typedef struct VkStrokePlan {
+    int32_t n_sets, n_strokes, n_segments, reserved;
+    VkStrokeSet set[VK_OVERLAY_MAX_SETS];
+    VkStroke stroke[VK_OVERLAY_MAX_STROKES];
+    VkStrokeSegment seg[VK_OVERLAY_MAX_SEGMENTS];
+} VkStrokePlan;
+int vk_stroke_overlay_u8(const void* in, void* out, const int32_t* set_of_frame, const VkStrokePlan* plan /* HOST memory */, int32_t n,
+                         int32_t H, int32_t W, void* stream);
+
 /* library info */
 int vk_abi_version(void);
 /* ABI v7: the 16-bit storage type this library was built for: 0 = bf16 (libvista_hip.so, the default and the BASELINE config's dtype), 1 = IEEE fp16

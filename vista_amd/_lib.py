@@ -69,6 +69,26 @@ class VkRowBoxes(C.Structure):
     _fields_ = [("n", _i32), ("reserved", _i32), ("box", VkRowBox * VK_RESHARD_MAX_BOXES)]
 
 
+VK_OVERLAY_MAX_SETS, VK_OVERLAY_MAX_STROKES, VK_OVERLAY_MAX_SEGMENTS = 8, 32, 64
+
+
+class VkStrokeSegment(C.Structure):
+    _fields_ = [("ax", _f32), ("ay", _f32), ("bx", _f32), ("by", _f32), ("inv_len2", _f32)]
+
+
+class VkStroke(C.Structure):
+    _fields_ = [("color", _f32 * 3), ("alpha", _f32), ("r", _f32), ("seg_begin", _i32), ("seg_count", _i32)]
+
+
+class VkStrokeSet(C.Structure):
+    _fields_ = [("stroke_begin", _i32), ("stroke_count", _i32)]
+
+
+class VkStrokePlan(C.Structure):
+    _fields_ = [("n_sets", _i32), ("n_strokes", _i32), ("n_segments", _i32), ("reserved", _i32), ("set", VkStrokeSet * VK_OVERLAY_MAX_SETS),
+                ("stroke", VkStroke * VK_OVERLAY_MAX_STROKES), ("seg", VkStrokeSegment * VK_OVERLAY_MAX_SEGMENTS)]
+
+
 ABI_VERSION = 9  # vk_abi_version() of the library this table mirrors
 
 # name -> argtypes; every entry returns int. Must list every symbol include/vista_hip.h declares
@@ -128,6 +148,7 @@ SIGNATURES = {
     "vk_frame_fidelity_ws_bytes": [_i32, _i32],
     "vk_frame_fidelity_u8": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _vp],
     "vk_copy_row_boxes": [_vp, _vp, C.POINTER(VkRowBoxes), _i64, _i64, _i32, _vp],
+    "vk_stroke_overlay_u8": [_vp, _vp, _vp, C.POINTER(VkStrokePlan), _i32, _i32, _i32, _vp],
     "vk_abi_version": [],
     "vk_act_dtype": [],
 }

@@ -1394,3 +1394,63 @@ def copy_row_boxes(src, dst, boxes):
     check(_lib.load().vk_copy_row_boxes(_p(src), _p(dst), C.byref(rb), src.shape[0], dst.shape[0], src.shape[1] * src.element_size(),
                                         _stream()), "vk_copy_row_boxes")
     return dst
+
+
+# ---- drive front door (csrc/overlay.hip) ----
+OVERLAY_MAX_SETS, OVERLAY_MAX_STROKES, OVERLAY_MAX_SEGMENTS = 8, 32, 64   # VK_OVERLAY_MAX_* of include/vista_hip.h
+
+
+def stroke_counts(sets):
+    """(sets, strokes, segments) a list of stroke sets occupies in a plan."""
+    return len(sets), sum(len(s) for s in sets), sum(len(stroke[3]) for s in sets for stroke in s)
+
+
+def stroke_plan(sets):
+    """A list of stroke sets -> the VkStrokePlan the library reads. A set is a list of strokes (colour (3 floats in [0, 255]), alpha, r, segments),
+    a segment (ax, ay, bx, by) in pixel coordinates, a disc a segment with a == b. inv_len2 = 1 / |b - a|^2 is formed here in float32, one
+    rounding per operation (0 for a disc). The counts are stored whatever they are (the library refuses what exceeds VK_OVERLAY_MAX_*);
+    entries past the struct's capacity are not stored."""
+    import numpy as np
+    f = np.float32
+    plan = _lib.VkStrokePlan()
+    plan.n_sets, plan.n_strokes, plan.n_segments = stroke_counts(sets)
+    k = g = 0
+    for i, strokes in enumerate(sets):
+        if i < OVERLAY_MAX_SETS:
+            plan.set[i] = _lib.VkStrokeSet(k, len(strokes))
+        for colour, alpha, r, segments in strokes:
+            if k < OVERLAY_MAX_STROKES:
+                plan.stroke[k] = _lib.VkStroke((C.c_float * 3)(*[float(c) for c in colour]), float(alpha), float(r), g, len(segments))
+            k += 1
+            for ax, ay, bx, by in segments:
+                if g < OVERLAY_MAX_SEGMENTS:
+                    dx, dy = f(bx) - f(ax), f(by) - f(ay)
+                    l2 = dx * dx + dy * dy
+                    plan.seg[g] = _lib.VkStrokeSegment(float(ax), float(ay), float(bx), float(by), 0.0 if l2 == 0 else float(f(1) / l2))
+                g += 1
+    return plan
+
+
+def stroke_overlay(frames, sets, set_of_frame, out=None):
+    """vk_stroke_overlay_u8: frames (n, H, W, 3) uint8, dense, on the GPU -> the frames with anti-aliased strokes drawn in; frame i takes
+    sets[set_of_frame[i]], a value outside [0, len(sets)) (-1) copies it. `sets` is a list of stroke sets (stroke_plan) or a prebuilt VkStrokePlan,
+    `set_of_frame` a sequence of ints or an int32 tensor on the frames' device. `out` may be `frames` itself (in place); by default a new
+    tensor. The bytes equal the numpy float32 evaluation of the header's definition (tests/_overlay_ref.py)."""
+    _need(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"stroke_overlay: expected (n, H, W, 3) uint8 frames, got {tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise ValueError("stroke_overlay: frames must be a dense (contiguous) stack")
+    n, H, W, _ = frames.shape
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or out.device != frames.device or not out.is_contiguous():
+        raise ValueError("stroke_overlay: out must be a dense uint8 stack of the frames' shape on the frames' device")
+    if not torch.is_tensor(set_of_frame):
+        set_of_frame = torch.tensor([int(v) for v in set_of_frame], dtype=torch.int32, device=frames.device)
+    _need(set_of_frame, torch.int32, "set_of_frame")
+    if set_of_frame.dim() != 1 or set_of_frame.shape[0] != n or set_of_frame.device != frames.device or not set_of_frame.is_contiguous():
+        raise ValueError(f"stroke_overlay: set_of_frame must hold one int32 per frame ({n}) on the frames' device")
+    plan = sets if isinstance(sets, _lib.VkStrokePlan) else stroke_plan(sets)
+    check(_lib.load().vk_stroke_overlay_u8(_p(frames), _p(out), _p(set_of_frame), C.byref(plan), n, H, W, _stream()), "vk_stroke_overlay_u8")
+    return out

@@ -102,54 +102,80 @@ def _set_skip_encode(model, flag):
             emb.skip_encode = flag
 
 
+CARRY = 3   # frames handed from one window to the next
+
+
+def rollout_denoiser(model, fused=True):
+    """What a sampling round hands the sampler: the reference's closure (sample_utils.py:314-315), or a FusedDenoiser over the same two objects."""
+    def denoiser(x, sigma, cond, cond_mask):
+        return model.denoiser(model.model, x, sigma, cond, cond_mask)
+    if fused and isinstance(model.denoiser, Denoiser):
+        denoiser = FusedDenoiser(model.denoiser, model.model)
+    return denoiser
+
+
+def rollout_masks(num_frames, initial_cond_indices, device):
+    """-> (the first round's conditioning mask, every later round's: the carried frames)."""
+    first_mask = torch.zeros(num_frames, device=device)
+    first_mask[initial_cond_indices] = 1
+    carry_mask = torch.zeros(num_frames, device=device)
+    carry_mask[:CARRY] = 1
+    return first_mask, carry_mask
+
+
+def first_round(sampler, denoiser, c, uc, z, first_mask, noise_fn):
+    """Round 0: the window grows out of the initial conditioning frame(s); the sampler rescales cond_frame itself."""
+    sample = sampler(denoiser, noise_fn(z), cond=c, uc=uc, cond_frame=z, cond_mask=first_mask)
+    sample[0] = z[0]
+    return sample
+
+
+def next_round(model, sampler, denoiser, value_dict, sample, num_frames, carry_mask, get_condition, force_uc_zero_embeddings, device, noise_fn):
+    """A later round from the previous window `sample`: the decoded third-from-last frame goes to the image embedder, its latent to the concat
+    conditioning (no re-encode) -- both are written into `value_dict`, whose other entries are the round's -- and the last three latents are
+    carried over as conditioning frames. Returns the new window; its frames [CARRY:] are the round's contribution."""
+    tail_images = model.decode_first_stage(sample[-14:])
+    value_dict["cond_frames_without_noise"] = tail_images[[-CARRY]]
+    value_dict["cond_frames"] = sample[[-CARRY]] / model.scale_factor
+    _set_skip_encode(model, True)
+    try:
+        c, uc = get_condition(model, value_dict, num_frames, force_uc_zero_embeddings, device)
+    finally:
+        _set_skip_encode(model, False)
+    seeded = fill_latent(sample[-CARRY:], num_frames, list(range(CARRY)), device)
+    return sampler(denoiser, noise_fn(seeded), cond=c, uc=uc, cond_frame=seeded, cond_mask=carry_mask)
+
+
 @torch.no_grad()
 def do_sample(images, model, sampler, value_dict, num_rounds, num_frames, force_uc_zero_embeddings=None, initial_cond_indices=None,
               device="cuda", get_condition=None, noise_fn=None, fused=True):
     """-> (samples in [0,1], samples_z, images). Same contract as the reference's do_sample; two optional hooks on top:
     `get_condition(model, value_dict, num_frames, force_uc_zero_embeddings, device) -> (c, uc)` and `noise_fn(like)`
     (default torch.randn_like) so a test can feed the very noise a CPU reference run drew. `fused`: hand the sampler a
-    FusedDenoiser (its one-pass prepare/combine/Euler kernels) instead of the reference's opaque closure; same arithmetic."""
+    FusedDenoiser (its one-pass prepare/combine/Euler kernels) instead of the reference's opaque closure; same arithmetic.
+    The round bodies (first_round / next_round) are shared with vista_amd.drive.DriveSession, which holds a rollout open between rounds."""
     initial_cond_indices = [0] if initial_cond_indices is None else initial_cond_indices
     force_uc_zero_embeddings = [] if force_uc_zero_embeddings is None else force_uc_zero_embeddings
     get_condition = get_condition or getattr(model, "condition_fn", None)
     if get_condition is None:
         raise ValueError("do_sample: no conditioner -- build the pipeline with conditioner=GeneralConditioner(...) or pass get_condition=")
     noise_fn = noise_fn or torch.randn_like
-    carry = 3                                  # frames handed from one window to the next
+    carry = CARRY
     fresh = num_frames - carry                 # new frames every later round contributes
-
-    def denoiser(x, sigma, cond, cond_mask):  # the reference's closure (sample_utils.py:314-315)
-        return model.denoiser(model.model, x, sigma, cond, cond_mask)
-    if fused and isinstance(model.denoiser, Denoiser):
-        denoiser = FusedDenoiser(model.denoiser, model.model)
+    denoiser = rollout_denoiser(model, fused)
 
     with model.ema_scope("Sampling"):
         c, uc = get_condition(model, value_dict, num_frames, force_uc_zero_embeddings, device)
         z = model.encode_first_stage(images)
         samples_z = torch.zeros((num_rounds * fresh + carry,) + tuple(z.shape[1:]), device=device, dtype=z.dtype)
+        first_mask, carry_mask = rollout_masks(num_frames, initial_cond_indices, device)
 
-        first_mask = torch.zeros(num_frames, device=device)
-        first_mask[initial_cond_indices] = 1
-        carry_mask = torch.zeros(num_frames, device=device)
-        carry_mask[:carry] = 1
-
-        # round 0: the window grows out of the initial conditioning frame(s); the sampler rescales cond_frame itself
-        sample = sampler(denoiser, noise_fn(z), cond=c, uc=uc, cond_frame=z, cond_mask=first_mask)
-        sample[0] = z[0]
+        sample = first_round(sampler, denoiser, c, uc, z, first_mask, noise_fn)
         samples_z[:num_frames] = sample
 
         for n in range(1, num_rounds):
-            # re-condition: decoded third-from-last frame -> image embedder, its latent -> concat conditioning (no re-encode)
-            tail_images = model.decode_first_stage(sample[-14:])
-            value_dict["cond_frames_without_noise"] = tail_images[[-carry]]
-            value_dict["cond_frames"] = sample[[-carry]] / model.scale_factor
-            _set_skip_encode(model, True)
-            try:
-                c, uc = get_condition(model, value_dict, num_frames, force_uc_zero_embeddings, device)
-            finally:
-                _set_skip_encode(model, False)
-            seeded = fill_latent(sample[-carry:], num_frames, list(range(carry)), device)
-            sample = sampler(denoiser, noise_fn(seeded), cond=c, uc=uc, cond_frame=seeded, cond_mask=carry_mask)
+            sample = next_round(model, sampler, denoiser, value_dict, sample, num_frames, carry_mask, get_condition, force_uc_zero_embeddings,
+                                device, noise_fn)
             lo = n * fresh + carry
             samples_z[lo:lo + fresh] = sample[carry:]
 
