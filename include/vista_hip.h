@@ -409,6 +409,22 @@ int vk_frames_to_u8(const float* x, void* out, int32_t n_img, int32_t H, int32_t
 #define VK_FRAME_STATS_BLOCKS 16
 int vk_ensemble_frame_stats(const float* x, double* frame_sum, float* map, double* partial_ws, int32_t E, int32_t T, int32_t C, int32_t hw,
                             void* stream);
+/* vk_candidate_frame_stats: vk_ensemble_frame_stats for the ensembles of K candidate actions in one call, plus what a planner asks of them --
+ * every candidate's total and which one is smallest. Additive under ABI v9, as the two entries around it.
+ *   x          [K][E][T][C][hw] fp32, dense: the E members of each of K candidates. Frames [t0, T) are scored (T' = T - t0); the frames before
+ *              t0 -- a window's conditioning frames -- are never read.
+ *   frame_sum  [K][T'] fp64: frame_sum[k][t - t0] is bit for bit what vk_ensemble_frame_stats returns for frame t of candidate k alone (the same
+ *              element arithmetic, thread-to-element assignment, block reduction and fold of VK_FRAME_STATS_BLOCKS partials).
+ *   map        [K][T'][hw] fp32 or NULL: bitwise that entry's map.
+ *   total      [K] fp64: the candidate's frame sums added in frame order t0 .. T - 1 by one thread.
+ *   best       one int32: the index of the smallest total; ties go to the lowest index, a NaN total is never best, -1 when every total is NaN.
+ *   partial_ws K * T' * VK_FRAME_STATS_BLOCKS doubles of scratch, the caller's.
+ *   Two launches (statistics on a (VK_FRAME_STATS_BLOCKS, T', K) grid, then one block that folds and selects), no atomics: bitwise repeatable.
+ *   The 16-byte path and its alignment rule are vk_ensemble_frame_stats's (a function of hw alone).
+ *   VK_EINVAL: a NULL x / frame_sum / total / best / partial_ws, K < 1, E < 2, E > 64, t0 < 0, t0 >= T, C / hw <= 0, K > 65535, T' > 65535,
+ *   a misaligned x or map where hw % 4 == 0. */
+int vk_candidate_frame_stats(const float* x, double* frame_sum, double* total, int32_t* best, float* map, double* partial_ws, int32_t K,
+                             int32_t E, int32_t T, int32_t t0, int32_t C, int32_t hw, void* stream);
 /* vk_heat_overlay_u8: the input frames with a per-cell map blended in as a heat colour, ready to be written as 8-bit pictures.
  *   frames (n_img, 3, H, W) fp32 in [-1, 1] (16-byte aligned); map (n_img, H / cell, W / cell) fp32, >= 0; out (n_img, H, W, 3) uint8 (4-byte aligned).
  *   f   = 255 * (x + 1) / 2, the float vk_frames_to_u8(real = 1) forms before its cast

@@ -144,6 +144,7 @@ SIGNATURES = {
     "vk_lanczos_resize_u8": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "vk_frames_to_u8": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "vk_ensemble_frame_stats": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "vk_candidate_frame_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "vk_heat_overlay_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp],
     "vk_frame_fidelity_ws_bytes": [_i32, _i32],
     "vk_frame_fidelity_u8": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _vp],

@@ -1,7 +1,8 @@
 // Reward estimation front door (gfx950): what the ensemble knows beyond one scalar, and a picture of it.
 //   vk_ensemble_frame_stats : unbiased ensemble variance of E latents -> its sum per frame (fp64, fixed order) and its channel mean per pixel
+//   vk_candidate_frame_stats: the same statistics for K candidates' ensembles in one call + every candidate's total and the index of the smallest
 //   vk_heat_overlay_u8      : input frames blended towards a heat colour by that per-pixel map -> uint8 HWC frames
-// Both are HBM-bound element kernels without reuse: lanes walk the contiguous hw (or W) axis, 16 bytes per lane where the shape guarantees the
+// All are HBM-bound element kernels without reuse: lanes walk the contiguous hw (or W) axis, 16 bytes per lane where the shape guarantees the
 // alignment (hw % 4 == 0, W % 4 == 0), one element per lane otherwise; the only LDS is the block reduction of the frame sums.
 // No storage-type dependence: the same object code goes into both libraries.
 #include "common.h"
@@ -27,13 +28,13 @@ __device__ __forceinline__ float ens_var_at(const float* __restrict__ p, size_t 
     return d2 / (float)(E - 1);
 }
 
+// One block's share of one frame: xt = the frame in member 0 (member e lies e * member_stride floats further), m_frame = the frame's row of the map or
+// null, out = where this block's partial sum goes. Both kernels below are this body and nothing else, so a frame's numbers do not depend on
+// which of them produced it.
 template <int V>
-__global__ __launch_bounds__(RW_THREADS) void frame_stats_kernel(const float* __restrict__ x, float* __restrict__ map, double* __restrict__ partial,
-                                                                 int E, int T, int C, int hw) {
+__device__ __forceinline__ void frame_stats_block(const float* __restrict__ xt, size_t member_stride, float* __restrict__ m_frame,
+                                                  double* __restrict__ out, int E, int C, int hw) {
     __shared__ double red[RW_THREADS];
-    const int t = blockIdx.y;
-    const size_t frame = (size_t)C * hw, member_stride = (size_t)T * frame;
-    const float* xt = x + (size_t)t * frame;
     const int groups = hw / V;   // (V = 4 only where hw % 4 == 0)
     double acc = 0.0;
     for (int g = blockIdx.x * RW_THREADS + threadIdx.x; g < groups; g += VK_FRAME_STATS_BLOCKS * RW_THREADS) {
@@ -67,8 +68,8 @@ __global__ __launch_bounds__(RW_THREADS) void frame_stats_kernel(const float* __
                 msum[j] += v[j];
             }
         }
-        if (map) {
-            float* m = map + (size_t)t * hw + (size_t)g * V;
+        if (m_frame) {
+            float* m = m_frame + (size_t)g * V;
             if (V == 4) {
                 float4 o;
                 o.x = msum[0] / (float)C; o.y = msum[1] / (float)C; o.z = msum[2] / (float)C; o.w = msum[3] / (float)C;
@@ -84,7 +85,60 @@ __global__ __launch_bounds__(RW_THREADS) void frame_stats_kernel(const float* __
         if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0) partial[(size_t)t * VK_FRAME_STATS_BLOCKS + blockIdx.x] = red[0];
+    if (threadIdx.x == 0) *out = red[0];
+}
+
+template <int V>
+__global__ __launch_bounds__(RW_THREADS) void frame_stats_kernel(const float* __restrict__ x, float* __restrict__ map, double* __restrict__ partial,
+                                                                 int E, int T, int C, int hw) {
+    const int t = blockIdx.y;
+    const size_t frame = (size_t)C * hw;
+    frame_stats_block<V>(x + (size_t)t * frame, (size_t)T * frame, map ? map + (size_t)t * hw : nullptr,
+                         partial + (size_t)t * VK_FRAME_STATS_BLOCKS + blockIdx.x, E, C, hw);
+}
+
+// ---- the same statistics for K candidates' ensembles at once (the planner's round) ------------------------------------------------------------
+// x [K][E][T][C][hw]; block (b, tt, k) is block (b, t0 + tt) of frame_stats_kernel on candidate k's ensemble: frames before t0 are never read.
+template <int V>
+__global__ __launch_bounds__(RW_THREADS) void candidate_stats_kernel(const float* __restrict__ x, float* __restrict__ map,
+                                                                     double* __restrict__ partial, int E, int T, int t0, int C, int hw) {
+    const int tt = blockIdx.y, k = blockIdx.z, Ts = T - t0;
+    const size_t frame = (size_t)C * hw;
+    const size_t row = (size_t)k * Ts + tt;   // (k, tt) in frame_sum / map / partial
+    frame_stats_block<V>(x + ((size_t)k * E * T + (size_t)(t0 + tt)) * frame, (size_t)T * frame, map ? map + row * hw : nullptr,
+                         partial + row * VK_FRAME_STATS_BLOCKS + blockIdx.x, E, C, hw);
+}
+
+// One block: (1) a thread per (candidate, frame) adds the frame's partials in block order, as frame_stats_fold_kernel does; (2) a thread per
+// candidate adds its frame sums in frame order; (3) thread 0 picks the smallest total -- ties to the lowest index, a NaN never, -1 if all are NaN.
+__global__ __launch_bounds__(RW_THREADS) void candidate_fold_select_kernel(const double* __restrict__ partial, double* __restrict__ frame_sum,
+                                                                           double* __restrict__ total, int32_t* __restrict__ best, int K, int Ts) {
+    const long long rows = (long long)K * Ts;
+    for (long long r = threadIdx.x; r < rows; r += RW_THREADS) {
+        double a = 0.0;
+        for (int b = 0; b < VK_FRAME_STATS_BLOCKS; ++b) a += partial[(size_t)r * VK_FRAME_STATS_BLOCKS + b];
+        frame_sum[r] = a;
+    }
+    __syncthreads();   // (orders the block's global writes before its reads below)
+    for (int k = threadIdx.x; k < K; k += RW_THREADS) {
+        double a = 0.0;
+        for (int t = 0; t < Ts; ++t) a += frame_sum[(size_t)k * Ts + t];
+        total[k] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int arg = -1;
+        double least = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double v = total[k];
+            if (v != v) continue;
+            if (arg < 0 || v < least) {
+                arg = k;
+                least = v;
+            }
+        }
+        *best = arg;
+    }
 }
 
 // one thread per frame adds the frame's VK_FRAME_STATS_BLOCKS partials in block order
@@ -179,6 +233,26 @@ extern "C" int vk_ensemble_frame_stats(const float* x, double* frame_sum, float*
         hipLaunchKernelGGL(frame_stats_kernel<1>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, x, map, partial_ws, E, T, C, hw);
     VK_CHECK_LAUNCH();
     hipLaunchKernelGGL(frame_stats_fold_kernel, dim3((T + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const double*)partial_ws, frame_sum, T);
+    VK_CHECK_LAUNCH();
+    return VK_OK;
+}
+
+extern "C" int vk_candidate_frame_stats(const float* x, double* frame_sum, double* total, int32_t* best, float* map, double* partial_ws,
+                                        int32_t K, int32_t E, int32_t T, int32_t t0, int32_t C, int32_t hw, void* stream) {
+    if (!x || !frame_sum || !total || !best || !partial_ws || K < 1 || E < 2 || E > 64 || t0 < 0 || t0 >= T || C <= 0 || hw <= 0) return VK_EINVAL;
+    const int Ts = T - t0;
+    if (Ts > 65535 || K > 65535) return VK_EINVAL;   // (grid.y, grid.z)
+    const dim3 grid(VK_FRAME_STATS_BLOCKS, Ts, K);
+    // the rule of vk_ensemble_frame_stats: the path is a function of hw alone, and the 16-byte path needs its alignment
+    const bool vec = (hw % 4) == 0 && (((size_t)x) & 15) == 0 && (!map || (((size_t)map) & 15) == 0);
+    if ((hw % 4) == 0 && !vec) return VK_EINVAL;
+    if (vec)
+        hipLaunchKernelGGL(candidate_stats_kernel<4>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, x, map, partial_ws, E, T, t0, C, hw);
+    else
+        hipLaunchKernelGGL(candidate_stats_kernel<1>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, x, map, partial_ws, E, T, t0, C, hw);
+    VK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(candidate_fold_select_kernel, dim3(1), dim3(RW_THREADS), 0, (hipStream_t)stream, (const double*)partial_ws, frame_sum, total,
+                       best, K, Ts);
     VK_CHECK_LAUNCH();
     return VK_OK;
 }

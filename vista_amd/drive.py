@@ -30,7 +30,7 @@ angle / 780, goal / (1600, 900)); any combination of keys may share a round, {} 
 {images,grids,videos} under perform_save_locally's names, <save>/drive.jsonl (one line per scene: index, frames, seed, action, n_rounds, per round
 {"round", "action" as given, "frames": [lo, hi]}, timings) and, with --hud, <save>/hud/videos. The plain frames are always written unmodified.
 
-Not built: choosing actions by reward (a planner on fork()), and several GPUs (WORLD_SIZE > 1 is refused by name).
+Choosing the actions by reward is vista_amd.plan's (a Planner over a DriveSession). Not built: several GPUs (WORLD_SIZE > 1 is refused by name).
 """
 import collections
 import json
@@ -134,6 +134,7 @@ class DriveSession:
                  guider="TrianglePredictionGuider"):
         import torch
         self.model, self.n_frames, self.cond_aug = model, n_frames, cond_aug
+        self.guider, self.cfg_scale = guider, cfg_scale   # (what vista_amd.plan builds its scoring sampler from)
         self.inputs = SU.load_img_seq(frame_list, height, width, "cuda")
         cond_img = self.inputs[:1]
         self._cond_frames = cond_img + cond_aug * torch.randn_like(cond_img)
@@ -361,8 +362,17 @@ def main(argv=None):
     return _drive_loop(opt, entries)
 
 
-def _drive_loop(opt, entries):
-    """The loop of vista_amd.sample with a DriveSession in place of do_sample."""
+def _step_entries(session, entries, scene_action, timings, where):
+    """The rounds of a drive run: one step per script entry -> (the entries the record lists, nothing to add to its rounds)."""
+    for entry in entries:
+        session.step(entry_action(entry, scene_action))
+    return entries, None
+
+
+def _drive_loop(opt, entries, step_rounds=_step_entries, records_name="drive.jsonl", label="drive"):
+    """The loop of vista_amd.sample with a DriveSession in place of do_sample. `step_rounds(session, entries, scene_action, timings, where)` steps
+    the session len(entries) times and returns (the entry every round ran under, one dict per round to merge into the record's rounds, or
+    None); vista_amd.plan passes its own, which scores a list of candidates before every step, and writes plan.jsonl."""
     import torch
     from . import ops
     if opt.low_vram:
@@ -375,7 +385,7 @@ def _drive_loop(opt, entries):
     model = SU.init_model(spec)
     virtual_path, real_path = os.path.join(opt.save, "virtual"), os.path.join(opt.save, "real")
     os.makedirs(opt.save, exist_ok=True)
-    records_path = os.path.join(opt.save, "drive.jsonl")
+    records_path = os.path.join(opt.save, records_name)
     open(records_path, "w").close()   # the file describes this run only
 
     def clock():
@@ -393,12 +403,11 @@ def _drive_loop(opt, entries):
                                n_steps=opt.n_steps, cfg_scale=opt.cfg_scale, cond_aug=opt.cond_aug, eager=opt.eager,
                                guider="TrianglePredictionGuider" if len(entries) > 1 else "VanillaCFG")
         t1 = clock()
-        for entry in entries:
-            session.step(entry_action(entry, scene_action))
+        stepped, extras = step_rounds(session, entries, scene_action, timings, f"{opt.dataset} scene {sample_index}")
         t2 = clock()
         samples, inputs = session.frames(), session.inputs
         t3 = clock()
-        timings.update(load=t1 - t0, sample=t2 - t1, decode=t3 - t2)
+        timings.update(load=t1 - t0, sample=t2 - t1 - timings.get("score", 0.0), decode=t3 - t2)
         for path, frames in ((virtual_path, samples), (real_path, inputs)):
             for mode in ("videos", "grids", "images"):
                 SU.perform_save_locally(path, frames, mode, opt.dataset, sample_index)
@@ -410,10 +419,12 @@ def _drive_loop(opt, entries):
             os.makedirs(folder, exist_ok=True)
             SU.save_video(os.path.join(folder, f"{opt.dataset}_{sample_index:06}"), hud.cpu().numpy(), 10)
             timings["hud"] = clock() - t4
-        record = make_record(sample_index, frame_list, entries, seed=opt.seed, action=opt.action, n_frames=opt.n_frames, timings=timings)
+        record = make_record(sample_index, frame_list, stepped, seed=opt.seed, action=opt.action, n_frames=opt.n_frames, timings=timings)
+        for round_record, extra in zip(record["rounds"], extras or ()):
+            round_record.update(extra)
         with open(records_path, "a") as f:
             f.write(json.dumps(record, allow_nan=False) + "\n")
-        print(f"drive {sample_index}: {len(entries)} rounds, " + ", ".join(f"{k} {v:.2f} s" for k, v in timings.items()), flush=True)
+        print(f"{label} {sample_index}: {len(entries)} rounds, " + ", ".join(f"{k} {v:.2f} s" for k, v in timings.items()), flush=True)
 
         if opt.rand_gen:
             sample_index += random.randint(1, max(1, dataset_length - 1))

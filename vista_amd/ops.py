@@ -1306,6 +1306,30 @@ def ensemble_frame_stats(x, want_map=True):
     return frame_sum, fmap
 
 
+def candidate_frame_stats(x, t0, want_map=False):
+    """x (K, E, T, C, h, w) f32, the stacked members of K candidates' ensembles; frames [t0, T) are scored -> (frame_sum (K, T - t0) float64,
+    total (K,) float64, best 0-dim int32, map (K, T - t0, h, w) float32 or None): ensemble_frame_stats of every candidate's scored frames, bit
+    for bit, every candidate's frame sums added in frame order, and the index of the smallest total (ties to the lowest index, NaN never,
+    -1 if all are NaN) -- vk_candidate_frame_stats. Nothing is synchronised: all results stay on the GPU."""
+    _need(x, F32, "x")
+    if x.dim() != 6:
+        raise ValueError(f"candidate_frame_stats: expected (K, E, T, C, h, w) latents, got {tuple(x.shape)}")
+    if not isinstance(t0, int) or isinstance(t0, bool):
+        raise TypeError(f"candidate_frame_stats: t0 must be an int, got {t0!r}")
+    x = _aligned16(x)
+    K, E, T, Cn, h, w = x.shape
+    Ts = T - t0 if 0 <= t0 < T else 0   # (0: a t0 the entry refuses; the buffers below still hold one row)
+    rows = max(K * Ts, 1)
+    frame_sum = torch.empty(rows, dtype=torch.float64, device=x.device)[:K * Ts].view(K, Ts)
+    total = torch.empty(max(K, 1), dtype=torch.float64, device=x.device)[:K]
+    best = torch.empty((), dtype=torch.int32, device=x.device)
+    ws = torch.empty(rows * FRAME_STATS_BLOCKS, dtype=torch.float64, device=x.device)
+    fmap = torch.empty((K, Ts, h, w), dtype=F32, device=x.device) if want_map else None
+    check(_lib.load().vk_candidate_frame_stats(_p(x), _p(frame_sum), _p(total), _p(best), _p(fmap), _p(ws), K, E, T, t0, Cn, h * w, _stream()),
+          "vk_candidate_frame_stats")
+    return frame_sum, total, best, fmap
+
+
 def heat_overlay_u8(frames, fmap, vmax, alpha=0.6):
     """frames (n, 3, H, W) f32 in [-1, 1] and fmap (n, H / cell, W / cell) f32 >= 0 -> (n, H, W, 3) uint8: every frame blended towards the heat
     colour (255, 32, 0) with weight alpha * min(1, fmap / vmax) of its cell (vk_heat_overlay_u8; a zero map gives frames_to_u8(real=True)'s

@@ -130,19 +130,33 @@ def first_round(sampler, denoiser, c, uc, z, first_mask, noise_fn):
     return sample
 
 
+def next_round_inputs(model, sample, num_frames, device):
+    """What a later round takes from the previous window `sample`, whatever its action -> (cond_frames_without_noise: the decoded
+    third-from-last frame, for the image embedder; cond_frames: its latent, for the concat conditioning (no re-encode); seeded: the last three
+    latents as the conditioning frames of a zero window). One 14-frame decode."""
+    tail_images = model.decode_first_stage(sample[-14:])
+    seeded = fill_latent(sample[-CARRY:], num_frames, list(range(CARRY)), device)
+    return tail_images[[-CARRY]], sample[[-CARRY]] / model.scale_factor, seeded
+
+
+def next_round_condition(model, value_dict, num_frames, get_condition, force_uc_zero_embeddings, device):
+    """(c, uc) of a later round: `value_dict` holds the round's scalars and action and next_round_inputs' two conditioning frames; the first
+    stage embedder takes its frame as the latent it already is (skip_encode)."""
+    _set_skip_encode(model, True)
+    try:
+        return get_condition(model, value_dict, num_frames, force_uc_zero_embeddings, device)
+    finally:
+        _set_skip_encode(model, False)
+
+
 def next_round(model, sampler, denoiser, value_dict, sample, num_frames, carry_mask, get_condition, force_uc_zero_embeddings, device, noise_fn):
     """A later round from the previous window `sample`: the decoded third-from-last frame goes to the image embedder, its latent to the concat
     conditioning (no re-encode) -- both are written into `value_dict`, whose other entries are the round's -- and the last three latents are
-    carried over as conditioning frames. Returns the new window; its frames [CARRY:] are the round's contribution."""
-    tail_images = model.decode_first_stage(sample[-14:])
-    value_dict["cond_frames_without_noise"] = tail_images[[-CARRY]]
-    value_dict["cond_frames"] = sample[[-CARRY]] / model.scale_factor
-    _set_skip_encode(model, True)
-    try:
-        c, uc = get_condition(model, value_dict, num_frames, force_uc_zero_embeddings, device)
-    finally:
-        _set_skip_encode(model, False)
-    seeded = fill_latent(sample[-CARRY:], num_frames, list(range(CARRY)), device)
+    carried over as conditioning frames. Returns the new window; its frames [CARRY:] are the round's contribution. The two halves
+    (next_round_inputs: what depends on the window only; next_round_condition: what depends on the action too) are vista_amd.plan's as well,
+    which scores several actions from one window."""
+    value_dict["cond_frames_without_noise"], value_dict["cond_frames"], seeded = next_round_inputs(model, sample, num_frames, device)
+    c, uc = next_round_condition(model, value_dict, num_frames, get_condition, force_uc_zero_embeddings, device)
     return sampler(denoiser, noise_fn(seeded), cond=c, uc=uc, cond_frame=seeded, cond_mask=carry_mask)
 
 
