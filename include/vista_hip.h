@@ -127,7 +127,9 @@ int vk_gemm_fp8(const VkGemmDesc* desc, const float* a_scale, const float* w_sca
 
 /* The same GEMM with the round-2 options (all optional; vk_gemm_fp8(d, a_scale, w_scale, k_real) == {a_scale, w_scale, k_real, 0...}):
  *   a_mx / ld_mx     : MX block scales of the activations INSTEAD of a_scale: E8M0 bytes (2^(e-127)) [M][ld_mx], one per 32 consecutive
- *                      K-elements, applied inside v_mfma_scale_f32_32x32x64_f8f6f4; ld_mx % 4 == 0 and ld_mx * 32 >= d->K.
+ *                      K-elements, applied inside v_mfma_scale_f32_32x32x64_f8f6f4; ld_mx % 4 == 0 and ld_mx * 32 >= d->K. The kernel reads
+ *                      all d->K / 32 scale bytes of a row: the pad bytes past k_real / 32 multiply zero-filled activation chunks, so they
+ *                      must hold a finite E8M0 value (producers write 127 = 2^0), never 0xFF, the E8M0 NaN.
  *   mx_out / ld_mx_out: EPI_GEGLU only: write the gated output as MX fp8 -- d->out = e4m3 bytes [M][d->ldc], mx_out = E8M0 [M][ld_mx_out],
  *                      one scale per 32 output columns, chosen in the epilogue (2^e >= max|h| / 448) -- so that the FeedForward's second
  *                      GEMM (a_mx = this mx_out) needs no quantisation pass (attention.py:85-128). (N/2) % 32 == 0, ldc % 16 == 0.

@@ -19,6 +19,24 @@ extern "C" __global__ void probe_layout(const uint8_t* A, const uint8_t* B, floa
     }
 }
 
+// Summation error of the instruction alone: one wave, D[n][m] = sum_k A[n][k] * B[m][k] over K = 64 * steps, the accumulator chained through
+// `steps` instructions exactly as the K-loop of csrc/gemm_fp8.hip chains it (unit block scales, no other arithmetic). A, B: [32][K] bytes.
+extern "C" __global__ void probe_chain(const uint8_t* A, const uint8_t* B, float* D, int steps) {
+    const int lane = threadIdx.x;
+    const int r = lane & 31, kh = lane >> 5;
+    const int K = 64 * steps;
+    f32x16_t c = {0};
+    for (int s = 0; s < steps; ++s) {
+        const i32x8_t a = *(const i32x8_t*)(A + r * K + s * 64 + kh * 32);
+        const i32x8_t b = *(const i32x8_t*)(B + r * K + s * 64 + kh * 32);
+        c = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
+    }
+    for (int reg = 0; reg < 16; ++reg) {
+        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
+        D[row * 32 + r] = c[reg];
+    }
+}
+
 extern "C" __global__ __launch_bounds__(256) void probe_rate(float* out, int iters) {
     i32x8_t a, b;
     for (int i = 0; i < 8; ++i) { a[i] = 0x38383838 + threadIdx.x; b[i] = 0x30303030 + i; }
