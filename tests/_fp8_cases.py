@@ -50,6 +50,7 @@ import torch.nn.functional as F
 
 from tests import _bf16_cases as bc
 from tests import _parity_bodies as pb
+from tests._guard import rehome_pack
 from tests._bf16_cases import (BF16, F32, F64, LOG2E, Case, G, I, Norm, attn_ref, bitcut_cast, check, conv3x3_ref, conv_t3_ref, d,  # noqa: F401
                                drop_k, gelu64, last_tile_rows, ln_fold_ref, r16, r32, rel_l2, splice_last_tile, storage_cast, to_device, truncate_cast)
 
@@ -358,7 +359,7 @@ def _dense_strided():
     M, N, K = 260, 320, 320
 
     def run(ops, i):
-        buf = torch.zeros(M, 2 * N, dtype=BF16, device=i.a8.device)
+        buf = ops.torch.zeros(M, 2 * N, dtype=BF16, device=i.a8.device)   # (inside guarded(ops): an arena)
         ops.linear_fp8(_A(i), i.a_scale, _pack_linear(ops, i), out=buf[:, N:])
         assert not buf[:, :N].any(), "the columns outside the output block must stay 0, bit for bit"
         return [buf]
@@ -598,7 +599,7 @@ def _mx8(M, C):
         return [y[:, 2 * C:].contiguous(), y[:, :2 * C].contiguous()]
 
     def run(ops, i):
-        v, c8, cs = ops.linear(i.x, ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta)), ln=ops.rowstats(i.x), mx8_cols=2 * C)
+        v, c8, cs = ops.linear(i.x, rehome_pack(ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta))), ln=ops.rowstats(i.x), mx8_cols=2 * C)
         return [v, (c8, cs)]
     add(f"fp8_mx8_qkv_lnfold_{M}x{C}", build, ref, run, [("A", BF16), ("MX",)], kbreak=drop_k(), group="mx8")
 

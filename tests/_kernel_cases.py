@@ -11,6 +11,10 @@ A case is (build, ref64, run):
                      each in its true dtype (the storage type, bf16 for an alt_cols_from V block, fp32).
 `specs` names the bound of every output. Nothing here touches a GPU at import time.
 
+The GPU modules run every case on poisoned outputs inside guard bands (tests/_guard.py; tests/_parity_bodies.py: case_under_tile): `inputs` are
+arena copies, the ops.* calls allocate arenas, and run() re-homes what a pack builds outside the allocation factories (rehome_pack: the colsum
+of a LayerNorm fold, pack_ff_out) and takes a scratch copy of the one operand an entry point is declared to write (scratch).
+
 Bounds (derived, never taken from the code under test):
   A   single-rounding kernels. With u = 2^-11 (fp16; 2^-8 for a bf16 output) BOTH
         1. |out - ref| <= 1.25 u |ref| + (u / 4) rms(ref) for EVERY element (round-to-nearest is within u relative of the fp32 value; fp32
@@ -32,6 +36,8 @@ import types
 
 import torch
 import torch.nn.functional as F
+
+from tests._guard import rehome_pack, scratch
 
 F16, BF16, F32, F64 = torch.float16, torch.bfloat16, torch.float32, torch.float64
 TILE_CFGS = (0, 1, 2, 3, 4, 5, 7)
@@ -563,7 +569,7 @@ def make_cases(st):
             return [torch.cat([torch.zeros(M, N, dtype=F64), d(i.big[:, K:2 * K]) @ d(i.w).t()], 1)]
 
         def run(ops, i):
-            buf = torch.zeros(M, 2 * N, dtype=ST, device=i.big.device)
+            buf = ops.torch.zeros(M, 2 * N, dtype=ST, device=i.big.device)   # (inside guarded(ops): an arena)
             ops.linear(i.big[:, K:2 * K], ops.pack_linear(i.w, None), out=buf[:, N:])
             assert not buf[:, :N].any(), "the columns outside the output block must stay 0, bit for bit"
             return [buf]
@@ -610,7 +616,7 @@ def make_cases(st):
             return [y[:, :2 * C].contiguous(), y[:, 2 * C:].contiguous()]
 
         def run(ops, i):
-            y = ops.linear(i.x, ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta)), ln=ops.rowstats(i.x), alt_cols_from=2 * C)
+            y = ops.linear(i.x, rehome_pack(ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta))), ln=ops.rowstats(i.x), alt_cols_from=2 * C)
             return [y[:, :2 * C].contiguous(), y[:, 2 * C:].contiguous().view(BF16)]
         add(f"alt_qkv_lnfold_C{C}_M{M}", build, ref, run, [("A", ST), ("A", BF16)], tiles=True, kbreak=drop_k())
 
@@ -621,7 +627,7 @@ def make_cases(st):
             g = G(C + M)
             return I(x=r16(g, M, C, shift=0.3), w=r16(g, 3 * C, C, scale=C ** -0.5), b=r32(g, 3 * C), gamma=r32(g, C, scale=0.2, shift=1.0), beta=r32(g, C, scale=0.3))
         add(f"qkv_lnfold_C{C}_M{M}", build, lambda i: [ln_fold_ref(i.x, i.w, i.b, i.gamma, i.beta)],
-            lambda ops, i: [ops.linear(i.x, ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta)), ln=ops.rowstats(i.x))], [("A", ST)], tiles=True, kbreak=drop_k())
+            lambda ops, i: [ops.linear(i.x, rehome_pack(ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta))), ln=ops.rowstats(i.x))], [("A", ST)], tiles=True, kbreak=drop_k())
 
 
     for _C in (320, 640):
@@ -670,7 +676,7 @@ def make_cases(st):
 
         def run(ops, i):
             if fold:
-                return [ops.linear(i.x, ops.pack_geglu(i.w, i.b, ln=Norm(i.gamma, i.beta)), ln=ops.rowstats(i.x))]
+                return [ops.linear(i.x, rehome_pack(ops.pack_geglu(i.w, i.b, ln=Norm(i.gamma, i.beta))), ln=ops.rowstats(i.x))]
             return [ops.linear(i.x, ops.pack_geglu(i.w, i.b))]
         add(("geglu_lnfold" if fold else "geglu") + f"_{M}x{C}", build, ref, run, [("A", ST)], tiles=True, kbreak=drop_k())
 
@@ -818,10 +824,10 @@ def make_cases(st):
             return [y, y]
 
         def run(ops, i):
-            pin = ops.pack_geglu(i.w1, i.b1, ln=Norm(i.gamma, i.beta) if ln else None)
+            pin = rehome_pack(ops.pack_geglu(i.w1, i.b1, ln=Norm(i.gamma, i.beta) if ln else None))
             st = ops.rowstats(i.x) if ln else None
             kw = {} if mode == "plain" else (dict(res1=i.x) if mode == "res" else dict(res1=i.x, alpha=0.4, res2=i.xm, rowvec2=i.rv2, beta=0.6, rows_per_vec=S))
-            return [ops.ff_fused(i.x, pin, ops.pack_ff_out(i.w2, i.b2), ln=st, **kw), ops.linear(ops.linear(i.x, pin, ln=st), ops.pack_linear(i.w2, i.b2), **kw)]
+            return [ops.ff_fused(i.x, pin, rehome_pack(ops.pack_ff_out(i.w2, i.b2)), ln=st, **kw), ops.linear(ops.linear(i.x, pin, ln=st), ops.pack_linear(i.w2, i.b2), **kw)]
         key = f"ff_{M}_{'ln' if ln else 'noln'}_{mode}"
         add(key, build, ref, run, [("B", key + "/fused"), ("B", key + "/two_kernel")], group="ff")
 
@@ -843,7 +849,7 @@ def make_cases(st):
                      gamma=r32(g, C, scale=0.2, shift=1.0), beta=r32(g, C, scale=0.3))
 
         def run(ops, i):   # the row sums from both producers of the product path: the read-only pass and a GEMM epilogue (identity weight)
-            pw = ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta))
+            pw = rehome_pack(ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta)))
             x2, st = ops.linear(i.x, ops.pack_linear(torch.eye(C), None), emit_stats=True)
             assert torch.equal(x2, i.x)
             return [ops.linear(i.x, pw, ln=ops.rowstats(i.x)), ops.linear(x2, pw, ln=st)]
@@ -1152,7 +1158,7 @@ def make_cases(st):
             return [torch.cat([top, bot], 0), xr]
 
         def run(ops, i):
-            x = i.x.clone()
+            x = scratch(i.x, "x") if replace else i.x   # vk_sampler_prepare writes x with `replace` only: without, the embedded input is held unchanged
             net_in = ops.sampler_prepare(x, i.cf if replace else None, i.m if replace else None, i.uc if uc else None, i.cc, cpad, c_in, replace)
             return [net_in, x]
         # replace off: x * c_in is one exact product rounded once to fp32 and once more to 16 bits, as the reference's cast chain does: bitwise
@@ -1183,7 +1189,7 @@ def make_cases(st):
             return [x + (x - gd) / sig * (sign - sig)]
 
         def run(ops, i):
-            x = i.x.clone()
+            x = scratch(i.x, "x")   # the entry point's in / out operand
             ops.sampler_update(x, i.net, i.s, c_out, c_skip, sig, sign)
             return [x]
         add(f"sampler_update_{T}x{H * W}x{ld}", build, ref, run, [("F32",)], group="layout")

@@ -1,11 +1,18 @@
 """The storage-independent bodies of the two kernel parity modules (tests/test_f16_kernels_gpu.py, tests/test_bf16_kernels_gpu.py), each written
 once: a body takes the ops module inside the caller's ops.storage(...) context and the caller's case module fc (tests._f16_cases or
 tests._bf16_cases); whatever depends on the storage type -- the print tag, dtypes, ulp constants, alt_cols_from -- follows from fc.T.ST. Every
-body prints its figures (`F16PARITY ...` / `BF16PARITY ...`) before it asserts. Nothing here imports vista_amd or touches a GPU at import time."""
+body prints its figures (`F16PARITY ...` / `BF16PARITY ...`) before it asserts. Nothing here imports vista_amd or touches a GPU at import time.
+
+Every case runs on poisoned outputs inside guard bands (tests/_guard.py): case_under_tile runs its case inside guarded(ops) on embed(inputs) and
+ends with verify(); the hand-written bodies run inside the guarded context of their module's storage fixture, which verifies at teardown, and
+put their own operands into arenas (rnd). An element a kernel does not store is a NaN in the judged output, a store past an output, a
+statistics slab or a workspace a damaged guard, a load past an operand a NaN in the result, an input written without leave a failure."""
 import ctypes as C
 import math
 
 import torch
+
+from tests import _guard
 
 F16, BF16, F32 = torch.float16, torch.bfloat16, torch.float32
 
@@ -40,23 +47,29 @@ def judge(fc, case, outs, refs, tag):
     assert not fails, f"{case.name} {tag}: {fails}"
 
 
-def case_under_tile(ops, fc, case, cfg):
+def case_under_tile(ops, fc, case, cfg, device="cuda"):
+    """One run, on embedded inputs and poisoned outputs: judged against the float64 reference with the case's bounds, then every guard byte
+    and every input must be what it was. (device: tests/test_extent_cpu.py drives plain-torch stand-ins through this very body on the CPU.)"""
     i, refs = inputs_and_ref(fc, case)
-    ops.TILE_CFG = cfg
-    outs = case.run(ops, fc.to_device(i, "cuda"))
-    ops.TILE_CFG = 0
-    judge(fc, case, outs, refs, f"cfg{cfg}")
+    with _guard.guarded(ops):
+        ops.TILE_CFG = cfg
+        try:
+            outs = case.run(ops, _guard.embed(i, device))
+        finally:
+            ops.TILE_CFG = 0
+        judge(fc, case, outs, refs, f"cfg{cfg}")
+        _guard.verify()
 
 
 # ------------------------------------------------------------------------------------------------ helpers of the hand-written tests
 def rnd(fc, *shape, scale=1.0, seed=0, dtype=None):
     g = torch.Generator(device="cpu").manual_seed(seed + sum(shape))
-    return (torch.randn(*shape, generator=g) * scale).to(dtype or fc.T.ST).cuda()
+    return _guard.put((torch.randn(*shape, generator=g) * scale).to(dtype or fc.T.ST), label="rnd")
 
 
 def _norm(fc, Cc, seed=7):
     g = torch.Generator().manual_seed(seed)
-    return fc.Norm((1 + 0.2 * torch.randn(Cc, generator=g)).cuda(), (0.1 * torch.randn(Cc, generator=g)).cuda())
+    return fc.Norm(_guard.put(1 + 0.2 * torch.randn(Cc, generator=g), label="gamma"), _guard.put(0.1 * torch.randn(Cc, generator=g), label="beta"))
 
 
 def check_stats(fc, st, out):
@@ -95,16 +108,42 @@ def conv_t3_halo_frames_are_bitwise_the_slice_of_the_whole_clip(ops, fc):
 
 
 # ------------------------------------------------------------------------------------------------ split-K
+def _run_recording_choices(ops, case, ig):
+    """case.run with every GEMM launch's (K slices, M, N) recorded: vk_gemm_tile_choice asked about the very descriptor of the launch."""
+    asked, gemm = [], ops._gemm
+
+    def recording(desc, *a, **k):
+        ops._prepare(desc)
+        choice = ops._lib.load().vk_gemm_tile_choice(C.byref(desc))
+        assert choice > 0, choice
+        asked.append((choice % 16, desc.M, desc.N))
+        return gemm(desc, *a, **k)
+    ops._gemm = recording
+    try:
+        return case.run(ops, ig), asked
+    finally:
+        ops._gemm = gemm
+
+
 def splitk_with_and_without_workspace(ops, fc, name):
-    """Both runs within bound A / F32; the 16-bit results at most one ulp of the storage type apart (another fp32 summation order); the fp32
-    form repeatable bit for bit and NOT equal to the plain kernel's -- which proves that the split path ran."""
+    """The split runs with the workspace at exactly slices x M x N x 4 bytes (slices from vk_gemm_tile_choice, asked again at that size), its
+    back guard intact. Both runs within bound A / F32; the 16-bit results at most one ulp of the storage type apart (another fp32 summation
+    order); the fp32 form repeatable bit for bit -- across the two workspace sizes -- and NOT equal to the plain kernel's -- which proves that
+    the split path ran."""
     case = fc.BY_NAME[name]
     i, refs = inputs_and_ref(fc, case)
-    ig = fc.to_device(i, "cuda")
-    split = case.run(ops, ig)
-    again = case.run(ops, ig)
+    ig = _guard.embed(i)
+    again, asked = _run_recording_choices(ops, case, ig)          # the default workspace: what the launcher asks of each launch
+    # (the fp32-output launch is the one this body proves split, below; the launcher's rules keep the dense case's 16-bit launch whole)
+    assert len(asked) == 2 and asked[1][0] > 1, f"the launcher does not split this case: (slices, M, N) = {asked}"
+    ops.SPLITK_WS_BYTES = max(s * M * N * 4 for s, M, N in asked if s > 1)   # exactly what include/vista_hip.h states a split needs, behind it the back guard
+    ops._SPLITK_WS.ws.clear()
+    split, taken = _run_recording_choices(ops, case, ig)
+    print(f"{_tag(fc)} {name} split-K (slices, M, N)={asked} workspace={ops.SPLITK_WS_BYTES} bytes")
+    assert taken == asked, f"with the workspace at its stated size the launcher chose {taken}, not {asked}"
     ops.SPLITK_WS_BYTES = 0
-    plain = case.run(ops, ig)
+    plain, none = _run_recording_choices(ops, case, ig)
+    assert all(s == 1 for s, _, _ in none)
     judge(fc, case, split, refs, "split")
     judge(fc, case, plain, refs, "plain")
     # one ulp apart: both fp32 values lie within the F32 bound of the reference (asserted above), i.e. within 4e-5 (|ref| + rms) of each
@@ -133,7 +172,7 @@ def _kind_fn(ops, fc, kind, n, H, W, Cc):
     x = rnd(fc, M, Cc)
     x3 = x.view(n, S, Cc)
     res = rnd(fc, M, Cc, seed=3)
-    rv = rnd(fc, n, Cc, seed=5).float()
+    rv = _guard.put(rnd(fc, n, Cc, seed=5).float(), label="rowvec")
     if kind == "dense+res+stats":
         pw = ops.pack_linear(rnd(fc, Cc, Cc, scale=Cc ** -0.5, seed=1), rnd(fc, Cc, seed=2).float())
         return lambda **kw: ops.linear(x, pw, res1=res, rowvec=rv, rows_per_vec=S, emit_stats=True, **kw)
@@ -146,7 +185,7 @@ def _kind_fn(ops, fc, kind, n, H, W, Cc):
         pw = ops.pack_linear(rnd(fc, Cc, 4 * Cc, scale=(4 * Cc) ** -0.5, seed=1), rnd(fc, Cc, seed=2).float())
         return lambda **kw: ops.linear(h4, pw, res1=res, rowvec=rv, rows_per_vec=S, emit_stats=True, **kw)
     if kind == "qkv_lnfold":
-        pw = ops.pack_linear(rnd(fc, 3 * Cc, Cc, scale=Cc ** -0.5, seed=1), rnd(fc, 3 * Cc, seed=2).float(), ln=_norm(fc, Cc))
+        pw = _guard.rehome_pack(ops.pack_linear(rnd(fc, 3 * Cc, Cc, scale=Cc ** -0.5, seed=1), rnd(fc, 3 * Cc, seed=2).float(), ln=_norm(fc, Cc)))
         st = ops.rowstats(x)
         alt = {"alt_cols_from": 2 * Cc} if fc.T.ST is F16 else {}   # the fp16 build's q|k|v launch stores its V block as bf16; the bf16 build has no such field to set
         return lambda **kw: ops.linear(x, pw, ln=st, **alt, **kw)
@@ -155,7 +194,7 @@ def _kind_fn(ops, fc, kind, n, H, W, Cc):
         pw = ops.pack_linear(rnd(fc, Cc, 4 * Cc, scale=(4 * Cc) ** -0.5, seed=1), rnd(fc, Cc, seed=2).float())
         return lambda **kw: ops.linear(h4, pw, res1=res, alpha=0.4, res2=x, rowvec2=rv, beta=0.6, rows_per_vec=S, **kw)
     if kind == "geglu_lnfold":
-        pw = ops.pack_geglu(rnd(fc, 8 * Cc, Cc, scale=Cc ** -0.5, seed=1), rnd(fc, 8 * Cc, seed=2).float(), ln=_norm(fc, Cc))
+        pw = _guard.rehome_pack(ops.pack_geglu(rnd(fc, 8 * Cc, Cc, scale=Cc ** -0.5, seed=1), rnd(fc, 8 * Cc, seed=2).float(), ln=_norm(fc, Cc)))
         st = ops.rowstats(x)
         return lambda **kw: ops.linear(x, pw, ln=st, **kw)
     if kind.startswith("conv3x3"):
@@ -214,10 +253,11 @@ def gemm_stream_forced(ops, fc, kind):
     rv = fc.r32(g, (M + S - 1) // S, Cc)
     gamma, beta = fc.r32(g, Cc, scale=0.2, shift=1.0), fc.r32(g, Cc, scale=0.1)
     kw, ln = {}, None
+    xg = _guard.put(x, label="x")
     if kind.startswith("qkv"):
         ref = fc.ln_fold_ref(x, w, b, gamma, beta)
-        pw = ops.pack_linear(w.cuda(), b.cuda(), ln=fc.Norm(gamma.cuda(), beta.cuda()))
-        ln = ops.rowstats(x.cuda())
+        pw = _guard.rehome_pack(ops.pack_linear(w.cuda(), b.cuda(), ln=fc.Norm(gamma.cuda(), beta.cuda())))
+        ln = ops.rowstats(xg)
         if kind.endswith("alt"):
             kw["alt_cols_from"] = 2 * Cc
     else:
@@ -225,8 +265,7 @@ def gemm_stream_forced(ops, fc, kind):
         pw = ops.pack_linear(w.cuda(), b.cuda())
         if kind != "plain":
             ref = ref + fc.d(res) + fc.d(rv).repeat_interleave(S, 0)[:M]
-            kw.update(res1=res.cuda(), rowvec=rv.cuda(), rows_per_vec=S, emit_stats=True)
-    xg = x.cuda()
+            kw.update(res1=_guard.put(res, label="res1"), rowvec=_guard.put(rv, label="rowvec"), rows_per_vec=S, emit_stats=True)
     o6 = forced(ops, 6, lambda: ops.linear(xg, pw, ln=ln, **kw))
     o4 = forced(ops, 4, lambda: ops.linear(xg, pw, ln=ln, **kw))
     if isinstance(o6, tuple):
@@ -259,7 +298,7 @@ def emit_stats_are_the_sums_of_the_rounded_output(ops, fc, cfg):
     M, N, K = 777, 320, 320
     x = rnd(fc, M, K)
     pw = ops.pack_linear(rnd(fc, N, K, scale=K ** -0.5, seed=1), rnd(fc, N, seed=2).float())
-    r1, rv = rnd(fc, M, N, seed=4), rnd(fc, 3, N, seed=5).float()
+    r1, rv = rnd(fc, M, N, seed=4), _guard.put(rnd(fc, 3, N, seed=5).float(), label="rowvec")
     out, st = forced(ops, cfg, lambda: ops.linear(x, pw, res1=r1, rowvec=rv, rows_per_vec=(M + 2) // 3, emit_stats=True))
     assert out.dtype is fc.T.ST and st.M == M and st.t.shape == (st.parts, M, 2)
     check_stats(fc, st, out)
@@ -277,8 +316,8 @@ def conv_epilogue_groupnorm_statistics(ops, fc):
     gn = ops.GnPartials()
     out = forced(ops, 7, lambda: ops.conv3x3(x, pw, n, H, W, res1=res, gn=gn)[0])
     assert gn.t is not None and gn.nchunks == S // 64 and torch.equal(out, base)
-    sums = torch.empty(n * 64, dtype=F32, device="cuda")
-    ops.check(ops._lib.load().vk_groupnorm_finalize_partials(ops._p(gn.t.clone()), ops._p(sums), n, gn.nchunks, 1, ops._stream()), "vk_groupnorm_finalize_partials")
+    sums = ops.torch.empty(n * 64, dtype=F32, device="cuda")   # (the fixture's guarded context: an arena)
+    ops.check(ops._lib.load().vk_groupnorm_finalize_partials(ops._p(_guard.scratch(gn.t, "partial")), ops._p(sums), n, gn.nchunks, 1, ops._stream()), "vk_groupnorm_finalize_partials")
     got = sums.view(n, 64).double().cpu()
     o = out.view(n, S, 32, Cc // 32).double().cpu()
     ref_s, ref_q = o.sum((1, 3)), o.pow(2).sum((1, 3))
@@ -299,7 +338,7 @@ def conv_epilogue_groupnorm_statistics(ops, fc):
 
 # ------------------------------------------------------------------------------------------------ norms: bitwise relation
 def groupnorm_cat_is_bitwise_groupnorm_of_the_concat(ops, fc, name):
-    i = fc.to_device(inputs_and_ref(fc, fc.BY_NAME[name])[0], "cuda")
+    i = _guard.embed(inputs_and_ref(fc, fc.BY_NAME[name])[0])
     silu = name.startswith("groupnorm_cat_3")
     got = ops.groupnorm_cat(i.a, i.b, i.gamma, i.beta, 1e-5, silu)
     want = ops.groupnorm(torch.cat([i.a, i.b], 2).contiguous(), i.gamma, i.beta, 1e-5, silu)
@@ -321,7 +360,7 @@ def attn_temporal_one_key_is_bitwise_v(ops, fc):
     """(B, T, S, heads) = (1, 1, 64, 2): one key, so P = 1 and the output is V itself, cast to the output type, bit for bit."""
     st = fc.T.ST
     qkv, v = _qkv(fc, 64, 2, 41)
-    o = ops.attn_temporal(qkv.cuda(), 1, 1, 64, 2)
+    o = ops.attn_temporal(_guard.put(qkv, label="qkv"), 1, 1, 64, 2)
     assert o.dtype is st and torch.equal(o.cpu(), v.float().to(st)), f"{int((o.cpu() != v.float().to(st)).sum())} of {o.numel()} elements differ from V"
 
 
@@ -332,10 +371,10 @@ def attn_temporal_narrow_store_is_bitwise_the_wide_store(ops, fc, B=2, T=7, S=9,
     st = fc.T.ST
     c = heads * 64
     rows = B * T * S
-    qkv = _qkv(fc, rows, heads, 43)[0].cuda()
+    qkv = _guard.put(_qkv(fc, rows, heads, 43)[0], label="qkv")
     wide = ops.attn_temporal(qkv, B, T, S, heads)
     sentinel = torch.tensor(-1234.0).to(st)
-    pad = torch.full((rows, c + 4), sentinel.item(), dtype=st, device="cuda")
+    pad = ops.torch.full((rows, c + 4), sentinel.item(), dtype=st, device="cuda")   # (the fixture's guarded context: an arena)
     assert pad.stride(0) % 8 == 4 and pad.stride(0) % 4 == 0
     ops.check(ops._lib.load().vk_attn_temporal_bf16(ops._p(qkv), ops._p(pad), B, T, S, heads, qkv.stride(0), c, 2 * c, pad.stride(0),
                                                      C.c_float(1.0 / math.sqrt(64)), ops._stream()), "vk_attn_temporal_bf16")

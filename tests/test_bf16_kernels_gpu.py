@@ -5,13 +5,18 @@ around every test, so the module also runs in a VISTA_ACT_DTYPE=fp16 process. Bo
 LN: measured on the MI355X + 25 %, B capped at 1.5 x the output-rounding floor (profiles/bf16_kernel_parity.txt); tests/test_bf16_bounds_cpu.py
 proves that the bounds separate a correct output from a truncated, bit-cut, K-dropped or double-rounded one -- which tests/test_kernels_gpu.py:
 close() (1.6e-2 |ref| + 2e-2 rms) does not. The shared checks are written once, in tests/_parity_bodies.py, and called here with this module's case
-table. Every test prints its figures (`BF16PARITY ...`) before it asserts."""
+table. Every test prints its figures (`BF16PARITY ...`) before it asserts.
+
+Every case runs on poisoned outputs inside guard bands (tests/_guard.py): the autouse storage fixture enters guarded(ops) around every test, so each
+output, statistics slab, weight pack and workspace ops.py allocates is the interior of an arena whose guards and whose unwritten bytes are 0xFF
+(NaN in every format used here), the operands are arena copies, and the fixture's teardown verifies every guard byte and every input."""
 import os
 
 import pytest
 import torch
 
 from tests import _bf16_cases as fc
+from tests import _guard
 from tests import _parity_bodies as pb
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +30,9 @@ def bf16_storage():
         pytest.fail("vista_amd/lib/libvista_hip.so is missing: __graft_entry__.build() links both storage variants")
     saved = (ops.TILE_CFG, ops.SPLITK_WS_BYTES)
     try:
-        with ops.storage(BF16):
+        with ops.storage(BF16), _guard.guarded(ops):   # every allocation of ops.py an arena: poisoned outputs inside guard bands
             yield ops
+            _guard.verify()                           # teardown: every guard byte intact, every embedded input unchanged
     finally:
         ops.TILE_CFG, ops.SPLITK_WS_BYTES = saved
 
@@ -118,7 +124,7 @@ def test_groupnorm_large_mean_routes(route, bf16_storage):
     ops = bf16_storage
     i = fc.gn_route_inputs()
     n, H, W, Cc = i.n, i.H, i.W, i.C
-    ig = fc.to_device(i, "cuda")
+    ig = _guard.embed(i)
     pw = ops.pack_conv3x3(ig.w, ig.b)
     gn = ops.GnPartials() if route == "conv_epilogue_partials" else None
     y = pb.forced(ops, 7, lambda: ops.conv3x3(ig.x, pw, n, H, W, gn=gn)[0]).view(n, H * W, Cc)

@@ -3,7 +3,11 @@ ops.storage(torch.float16) switches the enclosed ops.* calls to the fp16 library
 derived from the number formats; bound B: measured on the MI355X + 25 %, profiles/f16_kernel_parity.txt); tests/test_f16_bounds_cpu.py proves that
 the bounds separate a correct output from a broken one. The checks that do not depend on the storage type are written once, in
 tests/_parity_bodies.py, and called here with this module's case table; what only the fp16 build has stays here. Every test prints its figures
-(`F16PARITY ...`) before it asserts."""
+(`F16PARITY ...`) before it asserts.
+
+Every case runs on poisoned outputs inside guard bands (tests/_guard.py): the autouse storage fixture enters guarded(ops) around every test, so each
+output, statistics slab, weight pack and workspace ops.py allocates is the interior of an arena whose guards and whose unwritten bytes are 0xFF
+(NaN in fp16, bf16 and fp32 alike), the operands are arena copies, and the fixture's teardown verifies every guard byte and every input."""
 import ctypes as C
 import functools
 import os
@@ -12,6 +16,7 @@ import pytest
 import torch
 
 from tests import _f16_cases as fc
+from tests import _guard
 from tests import _parity_bodies as pb
 
 pytestmark = pytest.mark.gpu
@@ -26,8 +31,9 @@ def f16_storage():
         pytest.fail("vista_amd/lib/libvista_hip_f16.so is missing: __graft_entry__.build() links both storage variants")
     saved = (ops.TILE_CFG, ops.SPLITK_WS_BYTES)
     try:
-        with ops.storage(F16):
+        with ops.storage(F16), _guard.guarded(ops):   # every allocation of ops.py an arena: poisoned outputs inside guard bands
             yield ops
+            _guard.verify()                          # teardown: every guard byte intact, every embedded input unchanged
     finally:
         ops.TILE_CFG, ops.SPLITK_WS_BYTES = saved
 
@@ -142,16 +148,16 @@ def test_ff_fused_against_the_two_kernel_form(M, ln, mode, f16_storage):
     ops = f16_storage
     case = fc.BY_NAME[f"ff_{M}_{'ln' if ln else 'noln'}_{mode}"]
     i, _ = pb.inputs_and_ref(fc, case)
-    fus, two = case.run(ops, fc.to_device(i, "cuda"))
+    fus, two = case.run(ops, _guard.embed(i))
     dist = ((fus.double() - two.double()).norm() / two.double().norm()).item()
     print(f"F16PARITY {case.name} fused-vs-two-kernel rel_l2={dist:.4g} bound=0.002")
     assert dist < 2e-3
     if mode == "res":
-        ig = fc.to_device(i, "cuda")
-        pin = ops.pack_geglu(ig.w1, ig.b1, ln=fc.Norm(ig.gamma, ig.beta) if ln else None)
+        ig = _guard.embed(i)
+        pin = _guard.rehome_pack(ops.pack_geglu(ig.w1, ig.b1, ln=fc.Norm(ig.gamma, ig.beta) if ln else None))
         st = ops.rowstats(ig.x) if ln else None
         two, st2 = ops.linear(ops.linear(ig.x, pin, ln=st), ops.pack_linear(ig.w2, ig.b2), res1=ig.x, emit_stats=True)
-        fus2, stf = ops.ff_fused(ig.x, pin, ops.pack_ff_out(ig.w2, ig.b2), ln=st, res1=ig.x, emit_stats=True)
+        fus2, stf = ops.ff_fused(ig.x, pin, _guard.rehome_pack(ops.pack_ff_out(ig.w2, ig.b2)), ln=st, res1=ig.x, emit_stats=True)
         assert torch.equal(fus2, fus), "emitting the row sums changed the output"
         assert stf.parts == 2 and stf.t.shape == (2, M, 2)
         s2, sf = st2.t.sum(0), stf.t.sum(0)

@@ -8,13 +8,18 @@ K-dropped, double-rounded, wrongly scaled or wrongly quantised one -- which the 
 quantisation-error tests against the unquantised function ask a different question. Every figure is printed (`FP8PARITY ...`) before it is asserted.
 
 No bitwise equality between forced tile variants is asserted: csrc/gemm_fp8.hip promises none (its 128x128, 256x256 and 256x320 tiles share the
-K-loop order per output element, but nothing in the file states that as a contract)."""
+K-loop order per output element, but nothing in the file states that as a contract).
+
+Every case runs on poisoned outputs inside guard bands (tests/_guard.py): e4m3 codes, E8M0 and fp32 scales, bf16 outputs and row-sum slabs are arena
+interiors filled with 0xFF (NaN in each of these formats) before the launch, the operands are arena copies, and both tests/_parity_bodies.py:
+case_under_tile and this module's fixture verify every guard byte and every input after the run."""
 import os
 
 import pytest
 import torch
 
 from tests import _fp8_cases as fc
+from tests import _guard
 from tests import _parity_bodies as pb
 
 pytestmark = pytest.mark.gpu
@@ -28,8 +33,9 @@ def bf16_storage():
         pytest.fail("vista_amd/lib/libvista_hip.so is missing: __graft_entry__.build() links both storage variants")
     saved = (ops.TILE_CFG, ops.SPLITK_WS_BYTES)
     try:
-        with ops.storage(BF16):
+        with ops.storage(BF16), _guard.guarded(ops):   # every allocation of ops.py an arena: poisoned outputs inside guard bands
             yield ops
+            _guard.verify()                           # teardown: every guard byte intact, every embedded input unchanged
     finally:
         ops.TILE_CFG, ops.SPLITK_WS_BYTES = saved
 
