@@ -17,8 +17,23 @@ extern "C" {
 #endif
 
 /* ------------------------------------------------------------------ GEMM / implicit-GEMM convolution */
-enum { VK_AMODE_DENSE = 0, VK_AMODE_CONV3X3 = 1, VK_AMODE_TEMPORAL3 = 2, VK_AMODE_CONV3D = 3 };
+enum { VK_AMODE_DENSE = 0, VK_AMODE_CONV3X3 = 1, VK_AMODE_TEMPORAL3 = 2, VK_AMODE_CONV3D = 3, VK_AMODE_UPCONV2X2 = 4 };
 enum { VK_EPI_LINEAR = 0, VK_EPI_GEGLU = 1, VK_EPI_TRANS = 2 };
+/* VK_AMODE_UPCONV2X2 (added under ABI v9 without a version step: a new enum value, no field or meaning of VkGemmDesc changes): the Upsample of the UNet,
+ * nearest x2 followed by a 3x3 convolution with pad 1 (openaimodel.py:100-102), as FOUR 2x2 convolutions of the source image. Tap ky of output row
+ * 2i + a reads source row (2i + a + ky - 1) >> 1 -- i-1, i, i for a = 0 and i, i, i+1 for a = 1 -- and likewise in x, so output pixel (2i + a, 2j + b)
+ * is a 2x2 convolution whose window starts at source pixel (i + a - 1, j + b - 1) (zero padding of the SOURCE reproduces the borders exactly) and whose
+ * weights are sums of the nine taps: rows {w[0], w[1] + w[2]} for a = 0, {w[0] + w[1], w[2]} for a = 1, columns by the same rule with b. K = 4 Cin
+ * instead of 9 Cin at the same output rows; exact in real arithmetic.
+ *   A    NHWC source [n_img][H][Wd][Cin], Cin % 64 == 0;  H, Wd the source size, Hout = 2 H, Wout = 2 Wd, ups = 2, stride = 1, asym_pad = 0
+ *   Wt   four class packs one after another, class 2a + b at rows [(2a + b) * pad(N), (2a + b + 1) * pad(N)), each [pad(N)][Cin/64][2 dy + dx][64]
+ *        (vista_amd/ops.py: pack_upconv2x2 folds them in fp32 and rounds once); bias: one vector
+ *   out  [M][ldc], M = n_img * 4 H Wd output rows in the usual order; K = 4 Cin; rowvec with rows_per_vec = 4 H Wd
+ * The plain LINEAR epilogue only (bias, rowvec; 16-bit out): res1 / res2 / rowvec2, gnstat_out, rowstat_out, out_f32, mx8_out, ln_stats, act,
+ * alt_cols_from, halos and a row range are VK_EINVAL. It exists on the eight-wave pipelined 256x320 kernel alone (tile_cfg 0 or 7; + 8 = walk the
+ * tiles class-fastest instead of class-slowest, bitwise the same output): where the nine-tap form of the same layer would NOT run there as one launch
+ * without K slices (N % 320 != 0, too few rows to fill the chip, an operand of 4 GiB), every entry point returns VK_EINVAL and the caller runs
+ * VK_AMODE_CONV3X3 with ups = 2 on a nine-tap pack, which is unchanged. vk_gemm_tile_choice answers for it without a launch. */
 
 typedef struct VkGemmDesc {
     const void* A;       /* bf16 activations: [M][lda] (DENSE) or NHWC source image stack (conv modes)            */

@@ -6,6 +6,8 @@
 //                                            (openaimodel.py:198,232 ResBlock convs; :136 Downsample; :100-102 Upsample)
 //   TEMPORAL3  3x1x1 conv over frames, pad (1,0,0)   (video_model.py:38-52 time_stack)
 //   CONV3D     3x3x3 conv over (frames, H, W), pad 1 (temporal VAE decoder: autoencoding/temporal_ae.py:24-37,82-87)
+// (A fifth loader, UPCONV2X2 -- the Upsample's nearest x2 + 3x3 conv folded into four 2x2 class convs of the source, K = 4 Cin -- exists in
+//  gemm_pipe.hip only; this file validates it and plans it, or declines it so that the caller runs CONV3X3 with the fused upsample.)
 // W is [Npad][K] with K contiguous (= nn.Linear.weight layout; conv weights are packed [Cout][Cin/64][tap][64]: the K-loop walks all
 // taps of one 64-channel slab before the next slab, so a tile re-reads its input rows on CONSECUTIVE K-steps and they hit the XCD's L2.
 // With the tap-major order of round 1 ([Cout][tap][Cin]) the re-read came 5..20 K-steps x 32 workgroups later, missed the 4 MiB L2 and
@@ -583,7 +585,7 @@ inline bool pipe2_wanted(const VkGemmDesc* d, const TileChoice& t, bool gnstat) 
 }
 
 // ---- the launch plan: everything that decides which kernels a descriptor runs on, for the queries and for vk_gemm_bf16 alike ----
-enum GemmFamily { FAM_STREAM, FAM_PIPE2, FAM_PIPE, FAM_TILED };   // gemm_stream.hip, gemm_pipe2.hip, gemm_pipe.hip, gemm_kernel above
+enum GemmFamily { FAM_NONE = -1, FAM_STREAM, FAM_PIPE2, FAM_PIPE, FAM_TILED };   // declined (plan_for: VK_EINVAL); gemm_stream.hip, gemm_pipe2.hip, gemm_pipe.hip, gemm_kernel above
 struct GemmPlan {
     int family;
     int cfg;            // tile variant (TileChoice; 6 = the streaming kernel)
@@ -599,6 +601,18 @@ struct GemmPlan {
 GemmPlan plan_gemm(VkGemmDesc& d, bool rowstat, bool gnstat) {
     static const bool stream_on = [] { const char* e = getenv("VISTA_GEMM_STREAM"); return !e || atoi(e) != 0; }();   // A/B hook: 0 = tiled kernels only
     const int force = d.tile_cfg & 7;
+    // The folded upsample convolution exists on the pipelined kernel only. It is taken exactly where the NINE-TAP form of the same layer would run there as
+    // one launch without K slices (so the size rules, VISTA_GEMM_PIPE and the forced variant 7 of the tests apply unchanged) and the kernel takes the
+    // descriptor; anything else is declined and the caller runs the nine-tap form (the VAE decoder's widths, a rank whose M is small enough to split K).
+    if (d.amode == AMODE_UPCONV2X2) {
+        VkGemmDesc nine = d;
+        nine.amode = AMODE_CONV3X3;
+        nine.K = 9 * d.Cin;
+        nine.tile_cfg &= ~8;
+        const TileChoice t = choose_tile(&nine, false, false);
+        const bool ok = t.cfg == 7 && t.ksplit == 1 && !rowstat && !gnstat && vk_gemm_pipe_fit(&d);
+        return {ok ? FAM_PIPE : FAM_NONE, 7, 1, 0, 0, 0};
+    }
     // the streaming kernel: whole row range, not next to tile_cfg bit 4, and on its own choice (force == 0) never for a row-sum emitting launch
     if (d.m_begin == 0 && d.m_end == d.M && !(d.tile_cfg & 16) && (force == 6 || (stream_on && !rowstat))) {
         if (const int fit = vk_gemm_stream_fit(&d)) return {FAM_STREAM, 6, 1, 0, d.N / (32 * fit), 0};   // one slab per column tile: the workgroup combines its waves' row sums
@@ -678,13 +692,27 @@ int run_plan(const VkGemmDesc* d, const GemmPlan& p, hipStream_t stream) {
 
 inline int validate(const VkGemmDesc* d) {
     if (!d || !d->A || !d->Wt || !d->out) return VK_EINVAL;
-    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || (d->K % BK) != 0 || (d->N % 4) != 0 || d->tile_cfg < 0 || (d->tile_cfg & ~(64 | 16)) > 7) return VK_EINVAL;
+    const int upc_bits = d->amode == AMODE_UPCONV2X2 ? 8 : 0;   // (tile_cfg bit 3: the class-fastest tile order of the folded upsample convolution)
+    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || (d->K % BK) != 0 || (d->N % 4) != 0 || d->tile_cfg < 0 || (d->tile_cfg & ~(64 | 16 | upc_bits)) > 7) return VK_EINVAL;
+    if (d->amode < AMODE_DENSE || d->amode > AMODE_UPCONV2X2) return VK_EINVAL;
     if (d->m_begin < 0 || d->m_end < 0 || d->m_end > d->M || (d->m_end != 0 && d->m_begin >= d->m_end) || (d->m_end == 0 && d->m_begin >= d->M)) return VK_EINVAL;
     if ((d->m_begin != 0 || (d->m_end != 0 && d->m_end != d->M)) && d->epi == EPI_TRANS) return VK_EINVAL;   // (row ranges: LINEAR / GEGLU)
     if (d->amode != AMODE_DENSE && (d->Cin <= 0 || (d->Cin % BK) != 0)) return VK_EINVAL;
     if (d->amode == AMODE_DENSE && (d->lda % 8) != 0) return VK_EINVAL;
     if (d->amode == AMODE_CONV3X3 && (d->K != 9 * d->Cin || d->stride < 1 || d->stride > 2 || d->ups < 1 || d->ups > 2)) return VK_EINVAL;
     if (d->amode == AMODE_TEMPORAL3 && (d->K != 3 * d->Cin || d->T <= 0 || d->S <= 0)) return VK_EINVAL;
+    // The folded upsample convolution (vista_hip.h): four 2x2 class convolutions of the source, the plain LINEAR epilogue (bias, rowvec) and nothing else,
+    // on the pipelined 256x320 kernel only (variant 0 or 7; plan_gemm declines what that kernel does not take: the caller then runs the nine-tap form)
+    if (d->amode == AMODE_UPCONV2X2) {
+        if (d->K != 4 * d->Cin || d->ups != 2 || d->stride != 1 || d->asym_pad || d->H <= 0 || d->Wd <= 0 || d->Hout != 2 * d->H || d->Wout != 2 * d->Wd) return VK_EINVAL;
+        const long long hw4 = 4ll * d->H * d->Wd;
+        if ((d->M % hw4) != 0 || (d->rowvec && d->rows_per_vec != hw4)) return VK_EINVAL;
+        if (d->epi != EPI_LINEAR || d->out_f32 || d->res1 || d->res2 || d->rowvec2 || d->gnstat_out || d->rowstat_out || d->mx8_out || d->ln_stats || d->A2 ||
+            d->halo_prev || d->halo_next || d->act || d->alt_cols_from)
+            return VK_EINVAL;
+        if (d->m_begin != 0 || (d->m_end != 0 && d->m_end != d->M)) return VK_EINVAL;
+        if ((d->tile_cfg & (64 | 16)) != 0 || ((d->tile_cfg & 7) != 0 && (d->tile_cfg & 7) != 7)) return VK_EINVAL;
+    }
     if (d->amode == AMODE_CONV3D && (d->K != 27 * d->Cin || d->T <= 0 || d->H <= 0 || d->Wd <= 0 || d->H >= 4096 || d->Wd >= 4096 ||
                                      (long long)d->M != (long long)(d->M / (d->H * d->Wd)) * d->H * d->Wd)) return VK_EINVAL;
     if ((d->rowvec || d->rowvec2) && d->rows_per_vec <= 0) return VK_EINVAL;
@@ -714,7 +742,7 @@ int plan_for(const VkGemmDesc* d, VkGemmDesc& q, bool rowstat, bool gnstat, Gemm
     q = *d;
     norm_row_range(q);   // m_end = M unless the caller asked for a row range (validate() checked it)
     p = plan_gemm(q, rowstat || q.rowstat_out != nullptr, gnstat || q.gnstat_out != nullptr);
-    return VK_OK;
+    return p.family == FAM_NONE ? VK_EINVAL : VK_OK;
 }
 
 }  // namespace

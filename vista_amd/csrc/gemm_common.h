@@ -6,7 +6,7 @@
 
 namespace {
 
-enum { AMODE_DENSE = 0, AMODE_CONV3X3 = 1, AMODE_TEMPORAL3 = 2, AMODE_CONV3D = 3 };
+enum { AMODE_DENSE = 0, AMODE_CONV3X3 = 1, AMODE_TEMPORAL3 = 2, AMODE_CONV3D = 3, AMODE_UPCONV2X2 = 4 };
 enum { EPI_LINEAR = 0, EPI_GEGLU = 1, EPI_TRANS = 2 };
 
 constexpr int BK = 64;
@@ -501,9 +501,12 @@ __device__ __forceinline__ void gn_accumulate_quad(float (&gs)[NG], float (&gq)[
 // branch), because the sixteen-wave kernels live at the 128-VGPR cap with 64-80 accumulator registers: a residual that had to be spilled
 // would be WAITED for at the spill, which is exactly the serialisation this epilogue removes. Absent row vectors are staged as zeros and
 // added unconditionally (x + 0 is exact); the LayerNorm fold is a template flag (two more ds_reads and eight fmas per quad).
-template <int NRES, bool LN, bool MX, int FX, int FY, int FM, int FN, int BN, int CAP, int GNC = 0>
+// UPC (AMODE_UPCONV2X2, gemm_pipe.hip): the rows are the source pixels (img, i, j) of ONE parity class `cls` = 2a + b of a folded nearest-x2 upsample
+// convolution (p.M / m_end / rows_per_vec count class rows; p.H x p.Wd is the source image); everything is as for an ordinary LINEAR problem except
+// the row a lane STORES to, which is output pixel (2i + a, 2j + b) of the (2 H) x (2 Wd) image.
+template <int NRES, bool LN, bool MX, int FX, int FY, int FM, int FN, int BN, int CAP, int GNC = 0, bool UPC = false>
 __device__ __forceinline__ void epilogue_linear_lds_body(const VkGemmDesc& p, f32x16_t (&acc)[FX][FY], int m0, int n0, int wm, int wn, int l31, int lh,
-                                                         int stat_part, const float2* lnrow, const float* ev, int img0) {
+                                                         int stat_part, const float2* lnrow, const float* ev, int img0, int cls = 0) {
     constexpr int MW = FM * 32, NW = FN * 32, U = FX * FY;
     // ring depth: what fits beside the accumulators (16 registers per unit), ~36 registers of addresses / per-quad temporaries and the
     // 128-VGPR cap, at 8 registers per unit and residual tensor
@@ -530,6 +533,11 @@ __device__ __forceinline__ void epilogue_linear_lds_body(const VkGemmDesc& p, f3
         mrow[fj] = row_ok[fj] ? m : p.m_end - 1;  // loads of a row past M read the last row; only the stores are predicated
         if (NRES >= 1) rao[fj] = ((uint32_t)mrow[fj] * (uint32_t)lda_ + (uint32_t)wide_off) * 2u;
         if (NRES == 2) rbo[fj] = ((uint32_t)mrow[fj] * (uint32_t)p.ld_res2 + (uint32_t)wide_off) * 2u;
+        if constexpr (UPC) {
+            const int hw = p.H * p.Wd, img = mrow[fj] / hw, rem = mrow[fj] - img * hw, sy = rem / p.Wd, sx = rem - sy * p.Wd;
+            const uint32_t orow = (uint32_t)(img * 4 * hw + (2 * sy + (cls >> 1)) * 2 * p.Wd + 2 * sx + (cls & 1));
+            oo[fj] = (orow * (uint32_t)p.ldc + (uint32_t)wide_off) * 2u;   // (the host checked the range for all 4 M rows of the output)
+        } else
         oo[fj] = ((uint32_t)mrow[fj] * (uint32_t)p.ldc + (uint32_t)(wide_off - (p.mx8_out ? p.mx8_cols : 0))) * 2u;  // (MX tiles never use it)
     }
     static_assert(GNC == 0 || (MW % 64 == 0 && NW == 160 && NW % GNC == 0 && !MX), "gnstat_out: wave tiles of 64-row blocks x 160 columns of whole channel groups");
@@ -651,9 +659,13 @@ __device__ __forceinline__ void epilogue_linear_lds_body(const VkGemmDesc& p, f3
 // GN_CPG != 0: this kernel instantiation IS one of those that emit GroupNorm statistics of the output (VkGemmDesc.gnstat_out != NULL for every
 // launch of it: the pipelined kernel's CONV3X3 / TEMPORAL3 loaders, one tile per workgroup, no split-K) for groups of GN_CPG channels and GN_NRES
 // residual tensors, and carries that ONE body: two bodies behind a kernel-uniform branch already spill (40 bytes per lane), each alone takes 244 VGPRs
-template <int FX, int FY, int FM, int FN, int BN, int CAP = 128, int GN_CPG = 0, int GN_NRES = 0>
+template <int FX, int FY, int FM, int FN, int BN, int CAP = 128, int GN_CPG = 0, int GN_NRES = 0, bool UPC = false>
 __device__ __forceinline__ void gemm_epilogue_linear_lds(const VkGemmDesc& p, f32x16_t (&acc)[FX][FY], int m0, int n0, int wm, int wn, int l31, int lh,
-                                                         int stat_part, const float2* lnrow, const float* ev, int img0) {
+                                                         int stat_part, const float2* lnrow, const float* ev, int img0, int cls = 0) {
+    if constexpr (UPC) {   // (the launcher checked: no residual, LayerNorm fold, MX output, activation, row sums or GroupNorm statistics)
+        epilogue_linear_lds_body<0, false, false, FX, FY, FM, FN, BN, CAP, 0, true>(p, acc, m0, n0, wm, wn, l31, lh, stat_part, nullptr, ev, img0, cls);
+        return;
+    }
     if constexpr (GN_CPG != 0) {   // (the launcher checked: N = 32 GN_CPG, GN_NRES residuals, no LayerNorm fold / MX output / activation / row sums)
         epilogue_linear_lds_body<GN_NRES, false, false, FX, FY, FM, FN, BN, CAP, GN_CPG>(p, acc, m0, n0, wm, wn, l31, lh, stat_part, nullptr, ev, img0);
         return;

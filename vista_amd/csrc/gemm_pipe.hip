@@ -1,5 +1,6 @@
 // Eight-wave pipelined 256x320 variant of the tiled bf16 GEMM (tile_cfg 7): DENSE / CONV3X3 (stride 1 | 2, asymmetric pad, fused nearest x2
-// upsample) / TEMPORAL3 (no halo frames) loaders x LINEAR epilogue, DENSE x GEGLU, and the split-K form of the LINEAR ones; bf16 out.
+// upsample) / TEMPORAL3 (no halo frames) loaders x LINEAR epilogue, DENSE x GEGLU, and the split-K form of the LINEAR ones; bf16 out. Also the only
+// home of UPCONV2X2, the nearest-x2 upsample convolution folded into four 2x2 class convolutions (K = 4 Cin; plain LINEAR epilogue, no split-K).
 // Same math, LDS image, fragment layout and epilogues (gemm_common.h) as gemm.hip's sixteen-wave 256x320 kernel -- results are bitwise the
 // same -- but the K-step is written for the matrix pipe instead of for occupancy (measurements: profiles/r04_gemm_pipe.txt):
 //   * eight waves, wave tile 64 x 160 (2 activation x 5 weight fragments, 160 accumulator registers, 256-VGPR budget, two waves per SIMD):
@@ -58,7 +59,14 @@ template <int AMODE, int EPI, bool NT_A, bool SPLIT, int GN_CPG = 0, int GN_NRES
 __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, const int ksplit) {
     static_assert(!PF || AMODE == AMODE_DENSE, "the L2 prefetch is written for the dense loader");
     constexpr int LN_OFF = 2 * PSTAGE, EV_OFF = LN_OFF + PBM * 8;
-    constexpr int NTAPS = (AMODE == AMODE_CONV3X3) ? 9 : (AMODE == AMODE_TEMPORAL3) ? 3 : 1;
+    constexpr int NTAPS = (AMODE == AMODE_CONV3X3) ? 9 : (AMODE == AMODE_TEMPORAL3) ? 3 : (AMODE == AMODE_UPCONV2X2) ? 4 : 1;
+    // UPC: the folded nearest-x2 upsample convolution (vista_hip.h, VK_AMODE_UPCONV2X2). Output pixel (2i + a, 2j + b) of conv3x3(upsample2(x)) is a 2x2
+    // convolution of the SOURCE image with its window at (i + a - 1, j + b - 1) and class weights that are sums of the nine taps, so the launch is four
+    // LINEAR sub-problems -- one per parity class cls = 2a + b -- of M_c = n_img * H * Wd rows (source pixels) and K = 4 Cin each. The launcher hands the
+    // kernel the CLASS problem (upconv_class_desc: p.M = m_end = M_c, rows_per_vec = H * Wd, p.Wt = the first of the four class packs, p.out = the whole
+    // output); a workgroup's tile is (class, row tile, column tile) and only the epilogue's store row is remapped (gemm_common.h, UPC).
+    constexpr bool UPC = (AMODE == AMODE_UPCONV2X2);
+    static_assert(!UPC || (EPI == EPI_LINEAR && !SPLIT && GN_CPG == 0), "the folded upsample convolution: plain LINEAR epilogue, one launch");
     constexpr bool WALK = (EPI == EPI_GEGLU);   // persistent tile walk (pipe_launch); the LINEAR instantiations are compiled as one tile per workgroup
     __shared__ __attribute__((aligned(16))) char smem[2 * PSTAGE + PBM * 8 + epi_vec_floats(PBN) * 4];
 #ifdef PIPE_TIMING
@@ -79,9 +87,17 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     // SPLIT (small-M, deep-K LINEAR problems, as gemm.hip's split-K): workgroup = (K slice, tile), the K slice as the slow index; a slice's
     // fp32 partial tile goes to the workspace [slice][M][N] and gemm.hip's finishing pass applies the epilogue
     int kslice = 0;
+    int cls = 0;   // UPC: the parity class of this workgroup's tile
     auto tile_of = [&](const int bid, int& tm, int& tn) __attribute__((always_inline)) {
-        int logical = xcd_remap(bid, SPLIT ? ntiles * ksplit : ntiles);
+        int logical = xcd_remap(bid, SPLIT ? ntiles * ksplit : UPC ? ntiles * 4 : ntiles);
         if (SPLIT) { kslice = logical / ntiles; logical -= kslice * ntiles; }
+        // UPC tile order (tile_cfg bit 3): class-slowest = each class is an ordinary launch range; class-fastest = the four classes of a tile run side by
+        // side on an XCD (xcd_remap keeps consecutive logical tiles together), so three of the four reads of a source row block are L2 hits, at the
+        // price of four weight sets competing for that L2 (measurements: profiles/upconv_fold.txt)
+        if (UPC) {
+            if (p.tile_cfg & 8) { cls = logical & 3; logical >>= 2; }
+            else { cls = logical / ntiles; logical -= cls * ntiles; }
+        }
         if (tilesN < 8 || (long long)p.N * p.K * 2 <= (3LL << 20)) {
             tn = logical % tilesN;
             tm = logical / tilesN;
@@ -124,9 +140,32 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     unsigned voff_a[PAP];   // DENSE / TEMPORAL3: [0] only (the row groups are the uniform stride `apass` apart)
     amask_t amask = 0;      // CONV3X3: per piece 3 row-valid + 3 column-valid bits (tap (ky, kx) valid = row bit ky & column bit kx); TEMPORAL3: 3 frame bits
     auto setup = [&](const int m0, const int n0) __attribute__((always_inline)) {
-        rw = __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.Wt + (size_t)n0 * p.K), 0, (int)((unsigned)PBN * (unsigned)p.K * 2u), 0x00020000);
+        // (UPC: the four class packs lie one after another, each padded to ceil256(N) rows as every weight pack is -- N is a multiple of 320 here)
+        const size_t wrow0 = UPC ? (size_t)cls * (size_t)((p.N + 255) / 256 * 256) + (size_t)n0 : (size_t)n0;
+        rw = __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.Wt + wrow0 * p.K), 0, (int)((unsigned)PBN * (unsigned)p.K * 2u), 0x00020000);
         amask = 0;
-        if (AMODE == AMODE_DENSE) {
+        if (AMODE == AMODE_UPCONV2X2) {
+            // rows m = (img, i, j) over the source image; tap (dy, dx) reads source pixel (i + a - 1 + dy, j + b - 1 + dx): the lane offset is that of tap
+            // (0, 0) (it wraps for a row / column of -1, where it is only ever used with a valid tap's step added), the tap step is uniform
+            const int hw = p.H * p.Wd;
+            ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)((unsigned)p.M * (unsigned)p.Cin * 2u), 0x00020000);
+#pragma unroll
+            for (int i = 0; i < PAP; ++i) {
+                const int m = m0 + lr + PRPP * i;
+                const int img = m / hw;
+                const int rem = m - img * hw;
+                const int sy = rem / p.Wd, sx = rem - sy * p.Wd;
+                const int y0 = sy + (cls >> 1) - 1, x0 = sx + (cls & 1) - 1;
+                voff_a[i] = ((unsigned)((img * p.H + y0) * p.Wd + x0) * (unsigned)p.Cin + (unsigned)lsrc * 8u) * 2u;
+                unsigned mk = 0;   // per piece 2 row-valid + 2 column-valid bits
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    if (m < p.m_end && y0 + t >= 0 && y0 + t < p.H) mk |= 1u << t;
+                    if (x0 + t >= 0 && x0 + t < p.Wd) mk |= 4u << t;
+                }
+                amask |= (amask_t)mk << (4 * i);
+            }
+        } else if (AMODE == AMODE_DENSE) {
             const int rows = (p.m_end - m0 < PBM) ? p.m_end - m0 : PBM;
             ra = __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.A + (size_t)m0 * p.lda), 0,
                                                    (int)(((unsigned)(rows - 1) * (unsigned)p.lda + (unsigned)p.K) * 2u), 0x00020000);
@@ -198,6 +237,11 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
                 v = voff_a[j] + (unsigned)((ky * p.Wd + kx) * p.Cin) * 2u;
             }
             if (!ok) v = P_OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)c0b, 0, 0);
+        } else if (AMODE == AMODE_UPCONV2X2) {
+            const int dy = tap >> 1, dx = tap & 1;
+            const bool ok = ((amask >> (4 * j + dy)) & (amask >> (4 * j + 2 + dx)) & 1u) != 0;
+            const unsigned v = ok ? voff_a[j] + (unsigned)((dy * p.Wd + dx) * p.Cin) * 2u : P_OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)c0b, 0, 0);
         } else {
             const unsigned tapoff = (unsigned)((tap - 1) * p.S * p.Cin) * 2u;
@@ -409,7 +453,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
             q.rowvec2 = nullptr; q.ln_stats = nullptr; q.rowstat_out = nullptr; q.act = 0;
             gemm_epilogue<EPI_LINEAR, true, PFX, PFY, PFY, 5>(q, acc, m0, n0, e_wm, e_wn, e_l31, e_lh);
         } else if constexpr (EPI == EPI_GEGLU) gemm_epilogue_geglu_lds<PFX, PFY, PFY, 5, PBN>(p, acc, m0, n0, e_wm, e_wn, e_l31, e_lh, lnp, epi_vec);
-        else gemm_epilogue_linear_lds<PFX, PFY, PFY, 5, PBN, PCAP, GN_CPG, GN_NRES>(p, acc, m0, n0, e_wm, e_wn, e_l31, e_lh, tn * 2 + e_wn, lnp, epi_vec, eplan.img0);
+        else gemm_epilogue_linear_lds<PFX, PFY, PFY, 5, PBN, PCAP, GN_CPG, GN_NRES, UPC>(p, acc, m0, n0, e_wm, e_wn, e_l31, e_lh, tn * 2 + e_wn, lnp, epi_vec, eplan.img0, cls);
 #ifdef PIPE_TIMING
         unsigned long long tm_t2;
         asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tm_t2) :: "memory");
@@ -485,10 +529,43 @@ int pipe_launch(const VkGemmDesc* d, hipStream_t stream, int ksplit) {
     return VK_OK;
 }
 
+// AMODE_UPCONV2X2: the problem as the kernel sees it -- ONE parity class of the caller's descriptor (M = n_img * 4 H Wd output rows, rows_per_vec = 4 H Wd):
+// M_c = n_img * H * Wd rows of source pixels, the whole row range, a row vector per H * Wd rows
+inline VkGemmDesc upconv_class_desc(const VkGemmDesc* d) {
+    VkGemmDesc q = *d;
+    q.M = d->M / 4;
+    q.m_begin = 0;
+    q.m_end = q.M;
+    q.rows_per_vec = d->H * d->Wd;
+    return q;
+}
+
+// 1 = the kernel takes this (validated: gemm.hip) folded upsample convolution
+int upconv_fit(const VkGemmDesc* d) {
+    if (d->epi != EPI_LINEAR || d->out_f32 || (d->N % PBN) != 0 || d->mx8_out || d->A2 || d->res1 || d->res2 || d->rowvec2 || d->gnstat_out || d->rowstat_out ||
+        d->ln_stats || d->act || d->alt_cols_from || d->halo_prev || d->halo_next)
+        return 0;
+    if (d->m_begin != 0 || (d->m_end != 0 && d->m_end != d->M)) return 0;
+    VkGemmDesc q = *d;                 // the output's extent (all 4 M_c rows) with the class problem's rows per image: a 256-row tile of CLASS rows
+    q.rows_per_vec = d->H * d->Wd;     // must not span more images than the epilogue stages row vectors for
+    if (!epi_fast_everywhere(q, EPI_LINEAR, PBM)) return 0;
+    if ((unsigned long long)PBN * d->K * 2ull >= P_LIMIT) return 0;
+    return ((unsigned long long)(d->M / 4) * d->Cin * 2ull < P_LIMIT) ? 1 : 0;
+}
+
+int upconv_launch(const VkGemmDesc* d, hipStream_t stream) {
+    const VkGemmDesc q = upconv_class_desc(d);
+    const int tilesN = q.N / PBN, tilesM = (q.M + PBM - 1) / PBM;
+    hipLaunchKernelGGL((gemm_pipe_kernel<AMODE_UPCONV2X2, EPI_LINEAR, false, false>), dim3(4 * tilesM * tilesN), dim3(PNT), 0, stream, q, 1);
+    VK_CHECK_LAUNCH();
+    return VK_OK;
+}
+
 }  // namespace
 
 // 1 = the pipelined variant takes this (already validated) problem
 extern "C" int vk_gemm_pipe_fit(const VkGemmDesc* d) {
+    if (d->amode == AMODE_UPCONV2X2) return upconv_fit(d);
     if ((d->epi != EPI_LINEAR && d->epi != EPI_GEGLU) || d->out_f32 || (d->N % PBN) != 0 || d->mx8_out || d->A2) return 0;
     if (d->epi == EPI_GEGLU && d->amode != AMODE_DENSE) return 0;
     if (!epi_fast_everywhere(*d, d->epi, PBM)) return 0;   // the kernel carries the LDS-staged epilogues only
@@ -523,6 +600,7 @@ extern "C" int vk_gemm_pipe_gnstat_ok(const VkGemmDesc* d, int ksplit) {
 extern "C" int vk_gemm_pipe_launch(const VkGemmDesc* d, void* stream_, int ksplit) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!vk_gemm_pipe_fit(d)) return VK_EINVAL;
+    if (d->amode == AMODE_UPCONV2X2) return ksplit == 1 ? upconv_launch(d, stream) : VK_EINVAL;
     if (ksplit > 1 && (d->epi != EPI_LINEAR || !d->splitk_ws || d->ln_stats || d->rowstat_out || d->act)) return VK_EINVAL;
     if (d->gnstat_out && !vk_gemm_pipe_gnstat_ok(d, ksplit)) return VK_EINVAL;
     if (d->amode == AMODE_DENSE) return d->epi == EPI_GEGLU ? pipe_launch<AMODE_DENSE, EPI_GEGLU>(d, stream, ksplit) : pipe_launch<AMODE_DENSE, EPI_LINEAR>(d, stream, ksplit);

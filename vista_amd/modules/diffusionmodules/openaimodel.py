@@ -4,8 +4,10 @@
       h = conv(silu(GN32(x)))          vk_groupnorm_silu_bf16 -> implicit-GEMM 3x3 (or 3x1x1) conv
       h += Linear(silu(emb))[n]        per-image row vector added in that conv's epilogue
       h = conv(silu(GN32(h)))          second conv; `skip(x) + h` is its residual epilogue
-  Upsample (openaimodel.py:86-103): nearest x2 fused into the conv's gather; Downsample (:136): stride-2 gather.
+  Upsample (openaimodel.py:86-103): nearest x2 + 3x3 conv folded into four 2x2 class convs of the source (ops.upconv2x2; where the library declines
+  the shape, nearest x2 fused into the nine-tap conv's gather); Downsample (:136): stride-2 gather.
 """
+import os
 from typing import Iterable
 
 import torch.nn as nn
@@ -55,12 +57,26 @@ class Upsample(nn.Module, Packable):
         self.use_conv, self.dims = use_conv, dims
         self.conv = conv_nd(dims, self.channels, self.out_channels, kernel_size, padding=padding)
 
+    _nine = None   # (nine-tap pack, the folded pack it was built beside): built lazily, only for a shape the folded form declines
+
     def _pack(self, dev):
+        # VISTA_UPCONV_FOLD (default 1; 0 = the nine-tap form) is read when the module packs, so that every graph captured from one pack runs one form.
+        # Folded: four 2x2 class convolutions of the source image, 4/9 of the multiply-adds (ops.pack_upconv2x2), from the fp32 master weights.
+        if os.environ.get("VISTA_UPCONV_FOLD", "1") != "0" and self.channels % 64 == 0:
+            return ops.pack_upconv2x2(self.conv.weight, self.conv.bias, device=dev)
         return ops.pack_conv3x3(self.conv.weight, self.conv.bias, device=dev)
 
     def forward(self, x, H, W):
         assert x.shape[-1] == self.channels
-        out, Ho, Wo = ops.conv3x3(x, self.packed(), x.shape[0], H, W, ups=2)
+        pw = self.packed()
+        if pw.classes == 4:
+            if ops.upconv2x2_fits(x, pw, x.shape[0], H, W):
+                return ops.upconv2x2(x, pw, x.shape[0], H, W)
+            # a shape the pipelined kernel does not take (a narrow layer, a rank with few rows): the nine-tap form, its pack built on first use
+            if self._nine is None or self._nine[1] is not pw:
+                object.__setattr__(self, "_nine", (ops.pack_conv3x3(self.conv.weight, self.conv.bias, device=x.device), pw))
+            pw = self._nine[0]
+        out, Ho, Wo = ops.conv3x3(x, pw, x.shape[0], H, W, ups=2)
         return out, Ho, Wo
 
 

@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from ._lib import VkFp8Args, VkGemmDesc, check
 
-AMODE_DENSE, AMODE_CONV3X3, AMODE_TEMPORAL3, AMODE_CONV3D = 0, 1, 2, 3
+AMODE_DENSE, AMODE_CONV3X3, AMODE_TEMPORAL3, AMODE_CONV3D, AMODE_UPCONV2X2 = 0, 1, 2, 3, 4
 EPI_LINEAR, EPI_GEGLU, EPI_TRANS = 0, 1, 2
 # The 16-bit storage type of activations and packed weights: bf16 unless the process runs the fp16 build (VISTA_ACT_DTYPE=fp16, _lib.ACT_DTYPE).
 # `BF16` is the historical name used throughout this file for "the storage type"; ACT is the same object under an honest name.
@@ -98,11 +98,12 @@ class PackedWeight:
     """bf16 [ceil256(N)][K] weight (K contiguous) + f32 bias, laid out for vk_gemm_bf16. `colsum` (f32 [Np]) marks a weight with a
     LayerNorm folded in (pack_*_ln): wt = gamma (.) W, bias = W beta + b, colsum = row sums of the bf16-rounded wt."""
 
-    __slots__ = ("wt", "bias", "N", "K", "geglu", "colsum", "ln_eps", "ffout")
+    __slots__ = ("wt", "bias", "N", "K", "geglu", "colsum", "ln_eps", "ffout", "classes")
 
-    def __init__(self, wt, bias, N, K, geglu=False, colsum=None, ln_eps=0.0, ffout=False):
+    def __init__(self, wt, bias, N, K, geglu=False, colsum=None, ln_eps=0.0, ffout=False, classes=1):
         self.wt, self.bias, self.N, self.K, self.geglu, self.colsum, self.ln_eps = wt, bias, N, K, geglu, colsum, ln_eps
         self.ffout = ffout  # laid out for vk_ff_fused_bf16's out-projection (pack_ff_out): not a vk_gemm_bf16 operand
+        self.classes = classes  # 4: the class packs of a folded upsample convolution (pack_upconv2x2), one after another; only ops.upconv2x2 takes it
 
 
 def _finish_pack(w2d, bias, device, geglu=False, ln=None):
@@ -208,6 +209,50 @@ def pack_conv3x3(weight, bias=None, cin_pad=None, device="cuda"):
     if cp != cin:
         w = torch.nn.functional.pad(w, (0, cp - cin))
     return _finish_pack(_slab_major(w.reshape(cout, 9, cp)), None if bias is None else bias.detach().float(), device)
+
+
+UPCONV_ROWS = (((0,), (1, 2)), ((0, 1), (2,)))  # [parity a][dy] -> the taps ky of the 3x3 kernel that read source row i + a - 1 + dy
+
+
+def fold_upconv2x2(weight):
+    """conv3x3(pad 1) after a nearest x2 upsample as four 2x2 convolutions of the SOURCE image, one per output parity class (a, b): output pixel
+    (2i + a, 2j + b) reads source pixels (i + a - 1 + dy, j + b - 1 + dx), dy, dx in {0, 1}, because tap ky of an output row of parity a reads
+    source row (2i + a + ky - 1) >> 1 -- a = 0: i - 1, i, i; a = 1: i, i, i + 1 (UPCONV_ROWS), and likewise in x. Zero padding of the source
+    reproduces the borders (upsampled row -1 / 2H is source row -1 / H). [Cout][Cin][3][3] -> [4][Cout][Cin][2][2] in the arithmetic of `weight`
+    (fp32 in the packs, float64 in the tests), class index 2a + b; the taps are summed over ky first (in tap order), then over kx."""
+    w = weight.detach()
+    classes = []
+    for a in (0, 1):
+        rows = [sum(w[:, :, ky] for ky in UPCONV_ROWS[a][dy]) for dy in (0, 1)]          # [dy] -> [Cout][Cin][3 (kx)]
+        for b in (0, 1):
+            classes.append(torch.stack([torch.stack([sum(r[:, :, kx] for kx in UPCONV_ROWS[b][dx]) for dx in (0, 1)], -1) for r in rows], -2))
+    return torch.stack(classes)
+
+
+def pack_upconv2x2(weight, bias=None, device="cuda"):
+    """The Upsample convolution (openaimodel.py:100-102) for ops.upconv2x2: the 3x3 weight [Cout][Cin][3][3] folded in fp32 from the module's master
+    weights into the four class weights of fold_upconv2x2 (4/9 of the multiply-adds), rounded ONCE to the storage type, each class packed like a
+    conv weight with four taps -- [Cout][Cin/64][dy][dx][64], rows zero-padded as every pack -- and the four packs stored one after another in a
+    single allocation, class 2a + b at rows [(2a + b) * Np, (2a + b + 1) * Np); one bias vector."""
+    w = fold_upconv2x2(weight.detach().float())                      # [4][Cout][Cin][2][2]
+    _, cout, cin = w.shape[:3]
+    if cin % 64:
+        raise ValueError("pack_upconv2x2 needs Cin % 64 == 0")
+    Np = max(ceil_to(cout, 256), ceil_to(cout, 320))
+    wt = torch.zeros((4 * Np, 4 * cin), dtype=BF16, device=device)
+    for c in range(4):
+        wt[c * Np:c * Np + cout] = _slab_major(w[c].permute(0, 2, 3, 1).reshape(cout, 4, cin)).to(device=device, dtype=BF16)
+    b = None
+    if bias is not None:
+        b = torch.zeros((Np,), dtype=F32, device=device)
+        b[:cout] = bias.detach().to(device=device, dtype=F32)
+    return PackedWeight(wt, b, ceil_to(cout, 4), 4 * cin, classes=4)
+
+
+def unpack_upconv2x2(pw, cout):
+    """The class weights of a pack_upconv2x2 pack, in its storage type: [4][Cout][Cin][2][2] (tests; the references of the folded form)."""
+    Np, cin = pw.wt.shape[0] // 4, pw.K // 4
+    return pw.wt.view(4, Np, cin // 64, 2, 2, 64)[:, :cout].permute(0, 1, 2, 5, 3, 4).reshape(4, cout, cin, 2, 2)
 
 
 def pack_conv_t3(weight, bias=None, device="cuda", cin_pad=None):
@@ -568,6 +613,52 @@ def conv3x3(x, pw, n_img, H, W, *, stride=1, ups=1, out=None, out_f32=False, row
     _ask_gn(d, gn, Hout * Wout, x.device)   # gn: a GnPartials to fill with the GroupNorm statistics of `out` (the norm that follows this conv)
     _gemm(d)
     return (out.view(n_img, Hout * Wout, pw.N) if out.is_contiguous() else out), Hout, Wout
+
+
+# Tile order of the folded upsample convolution (VkGemmDesc.tile_cfg bit 3): 0 = class-slowest, 1 = class-fastest (csrc/gemm_pipe.hip; both measured in
+# profiles/upconv_fold.txt). Bitwise the same output either way.
+UPCONV_CLASS_FASTEST = int(os.environ.get("VISTA_UPCONV_ORDER", "0")) != 0
+
+
+def _upconv_desc(x, pw, n_img, H, W, rowvec, out):
+    cin = x.shape[-1]
+    d = VkGemmDesc()
+    d.A, d.lda = _p(x), cin
+    d.amode, d.epi = AMODE_UPCONV2X2, EPI_LINEAR
+    d.H, d.Wd, d.Cin, d.Hout, d.Wout, d.stride, d.ups = H, W, cin, 2 * H, 2 * W, 1, 2
+    _fill_epilogue(d, pw, out, n_img * 4 * H * W, rowvec, 4 * H * W, None, None, 1.0, 0.0)
+    stream = _prepare(d)
+    if UPCONV_CLASS_FASTEST:
+        d.tile_cfg |= 8
+    return d, stream
+
+
+def upconv2x2_fits(x, pw, n_img, H, W, rowvec=None, out=None):
+    """Does the library take the folded form of this upsample convolution (host arithmetic, no launch)? It does where the nine-tap form would run on
+    the pipelined 256x320 kernel in one launch: Cout % 320 == 0 and enough rows to fill the chip; else the caller runs ops.conv3x3(..., ups=2)."""
+    if out is None:
+        out = x   # (any 16-byte aligned device pointer: the answer depends on alignment and extents only)
+    d, _ = _upconv_desc(x, pw, n_img, H, W, rowvec, out)
+    d.ldc = pw.N
+    return _lib.load().vk_gemm_tile_choice(C.byref(d)) > 0
+
+
+def upconv2x2(x, pw, n_img, H, W, rowvec=None, out=None):
+    """Upsample.forward (openaimodel.py:100-102: nearest x2, then conv3x3 pad 1) on a pack_upconv2x2 pack: four 2x2 class convolutions of the source,
+    K = 4 Cin instead of 9 Cin, scattered to the output pixels of their parity. x (n_img, H*W, Cin) -> ((n_img, 4*H*W, Cout), 2H, 2W). Raises where the
+    library declines the shape (upconv2x2_fits): there is no quiet change of algorithm here."""
+    _need(x, BF16, "x")
+    if not x.is_contiguous():
+        raise ValueError("upconv2x2: x must be contiguous")
+    cin = x.shape[-1]
+    if pw.classes != 4 or pw.K != 4 * cin:
+        raise ValueError(f"upconv2x2: needs a pack_upconv2x2 weight with K = 4*{cin}")
+    M = n_img * 4 * H * W
+    if out is None:
+        out = torch.empty((M, pw.N), dtype=BF16, device=x.device)
+    d, stream = _upconv_desc(x, pw, n_img, H, W, rowvec, out)
+    check(_lib.load().vk_gemm_bf16(C.byref(d), stream), "vk_gemm_bf16 (folded upsample convolution)")
+    return (out.view(n_img, 4 * H * W, pw.N) if out.is_contiguous() else out), 2 * H, 2 * W
 
 
 def conv_t3(x, pw, T, S, *, out=None, out_f32=False, rowvec=None, res1=None, res2=None, alpha=1.0, beta=0.0, halo_prev=None,
