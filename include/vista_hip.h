@@ -115,6 +115,25 @@ typedef struct VkGemmDesc {
  *   vwm/modules/attention.py:85-92,117-121 (GEGLU FF), :344-346,421 (q,k,v,out), :579,602 (proj_in/out)
  *   vwm/modules/diffusionmodules/openaimodel.py:136 (Downsample), :84,100-102 (Upsample), :195-199,227-234 (ResBlock convs), :241 (skip)
  *   vwm/modules/diffusionmodules/video_model.py:38-52 (3x1x1 temporal conv), :148-157,176-182 (embedding MLPs), :189,438 (in/out conv) */
+/* Operand contract of vk_gemm_bf16 and its four plan queries (which hold every operand to this table alike: a query answers VK_EINVAL for an operand
+ * the launch would refuse. The shape rules of an epilogue -- ldc % 4, N % 32 for EPI_GEGLU, S % 4 for EPI_TRANS, which is what keeps that epilogue's
+ * 8-byte stores aligned -- are checked by vk_gemm_bf16 alone, as before: the queries answer for the shape as given):
+ * base alignment in bytes and leading-dimension multiple in elements, from the widest access any kernel the plan may pick makes to the operand.
+ * An operand outside its row is VK_EINVAL before any launch; what only a faster path needs is that path's to check, and it declines.
+ *   operand                              base   leading dimension        widest access
+ *   A, A2, halo_prev, halo_next, Wt      16     lda % 8, lda2 % 8        16-byte LDS-DMA / uint4 pieces (conv modes: rows of Cin % 64 elements)
+ *   out, 16-bit                          8      ldc % 4                  uint2 stores of the general epilogue (EPI_TRANS: rows of S % 4 keys, ldc unused)
+ *     ... 16 and ldc % 8 select the 16-byte stores and the LDS-staged epilogue; the pipelined (7, + 16) and streaming (6) kernels need them and
+ *     decline otherwise, as they do for a residual that is not 16-byte aligned with ld % 8
+ *   out, fp32 (out_f32)                  16     ldc % 4                  float4 stores
+ *   res1, res2                           8      ld_res1 % 4, ld_res2 % 4 uint2 loads
+ *   bias, ln_colsum                      16     -                        float4 loads (EPI_TRANS: 4, one float per lane)
+ *   rowvec, rowvec2                      16     ldv % 4                  float4 loads
+ *   ln_stats, rowstat_out                8      -                        float2 (sum, sum of squares)
+ *   gnstat_out                           4      -                        floats
+ *   splitk_ws                            16     -                        float4 partials
+ * The L2-prefetch variant of the pipelined kernel additionally wants A 128-byte aligned with lda % 64 == 0 and is bitwise the plain variant.
+ * vk_ff_fused_bf16: geglu->A 16 / lda % 8, both Wt 16, geglu->bias / ln_colsum 16, ln_stats 8; out_proj's out / res* / bias / rowvec* / rowstat_out as above. */
 int vk_gemm_bf16(const VkGemmDesc* d, void* stream);
 
 /* Number of partial-sum slabs vk_gemm_bf16 would write to d->rowstat_out for this problem (depends on the block tile the launcher
@@ -207,7 +226,9 @@ int vk_quantize_rows_fp8(const void* x, void* q, float* scale, int32_t M, int32_
  *   q, k : bf16, row (image*S + token) at q + row*ldq + head*64 (same for k / ldk)
  *   vt   : bf16 [n_img][heads][64][S]   (V transposed, produced by vk_gemm_bf16 EPI_TRANS)
  *   o    : bf16, row at o + row*ldo + head*64
- * S must be a multiple of 8. */
+ * S must be a multiple of 8.
+ * Operands (all three spatial entries): q, k, vt / v 16-byte aligned with ldq % 8, ldk % 8, ldv % 8 (16-byte pieces); o 8-byte aligned with ldo % 4
+ * (8-byte stores; the pipelined kernel of the pre-scaled form is taken only where o is 16-byte aligned with ldo % 8). Anything else: VK_EINVAL. */
 int vk_attn_spatial_bf16(const void* q, const void* k, const void* vt, void* o, int32_t n_img, int32_t heads,
                          int32_t S, int32_t ldq, int32_t ldk, int32_t ldo, float scale, void* stream);
 
@@ -227,7 +248,8 @@ int vk_attn_spatial_qkv_log2_bf16(const void* q, const void* k, const void* v, v
 /* Small dense attention, any head dim D in {64, 80, 128}: softmax(q k^T * scale) v per (image, head); q / k / v are column blocks of one
  * row-major buffer (q at qkv + row*ld + head*D, k at + k_off, v at + v_off; row = image*S + token). The nn.MultiheadAttention of the
  * conditioner's OpenCLIP ViT-H/14 image tower (FrozenOpenCLIPImageEmbedder, vwm/modules/encoders/modules.py:251-399: 257 tokens, 16 heads
- * of dim 80). 4*S*D bytes of LDS (<= 160 KiB). */
+ * of dim 80). 4*S*D bytes of LDS (<= 160 KiB).
+ * Operands: qkv and o 16-byte aligned, ld % 8, k_off % 8, v_off % 8, ldo % 8 (16-byte loads and stores); else VK_EINVAL. */
 int vk_attn_small_bf16(const void* qkv, void* o, int32_t n_img, int32_t heads, int32_t S, int32_t D, int32_t ld, int32_t k_off,
                        int32_t v_off, int32_t ldo, float scale, void* stream);
 
@@ -254,13 +276,16 @@ int vk_attn_spatial_fp8qk(const void* q8, const void* k8, const void* q_scales, 
 /* Temporal (cross-frame) self-attention over the T frames of every pixel: sequence length T <= 32, head dim 64.
  * Replaces the batchified xformers call at vwm/modules/attention.py:384-399 for VideoTransformerBlock.attn1
  * (vwm/modules/video_attention.py:116-127). Token rows are (b*T + t)*S + s; q,k,v are column blocks of one
- * row-major buffer: q at qkv + row*ld + head*64, k at + k_off, v at + v_off. */
+ * row-major buffer: q at qkv + row*ld + head*64, k at + k_off, v at + v_off.
+ * Operands: qkv 16-byte aligned, ld % 8, k_off % 8, v_off % 8 (16-byte loads); o 8-byte aligned, ldo % 4 (16-byte stores where o is 16-byte
+ * aligned with ldo % 8, else 8-byte ones); else VK_EINVAL. */
 int vk_attn_temporal_bf16(const void* qkv, void* o, int32_t B, int32_t T, int32_t S, int32_t heads, int32_t ld,
                           int32_t k_off, int32_t v_off, int32_t ldo, float scale, void* stream);
 
 /* Row softmax, fp32 scores -> bf16 probabilities: y[r][c] = softmax_c(x[r][:cols]). cols % 4 == 0, cols <= 16384.
  * Replaces `torch.nn.functional.softmax(w_, dim=2)` of the VAE decoder's single-head AttnBlock
- * (vwm/modules/diffusionmodules/model.py:160-166); q.k^T (scaled) and P.v run as vk_gemm_bf16 calls either side. */
+ * (vwm/modules/diffusionmodules/model.py:160-166); q.k^T (scaled) and P.v run as vk_gemm_bf16 calls either side.
+ * Operands: x 16-byte aligned, ldx % 4 (float4 loads); y 8-byte aligned, ldy % 4 (uint2 stores); else VK_EINVAL. */
 int vk_softmax_rows_f32_bf16(const float* x, void* y, int64_t rows, int32_t cols, int64_t ldx, int64_t ldy, void* stream);
 
 /* ------------------------------------------------------------------ normalisation */
@@ -273,7 +298,10 @@ int vk_softmax_rows_f32_bf16(const float* x, void* y, int64_t rows, int32_t cols
  * results are bitwise reproducible, no atomics). In the fp16-storage build this call and vk_groupnorm_silu_cat_bf16 take their sums about each
  * group's first element, so that E[x^2] - mean^2 does not cancel at a large |mean| / std, and refuse y == x (VK_EINVAL: every workgroup of a
  * group reads that element while the first one would overwrite it); the sums that cross the ABI below stay raw, so a norm fed by a GEMM
- * epilogue's partials or by sharded statistics -- most of the UNet's ResBlock norms -- is computed as before in both builds. */
+ * epilogue's partials or by sharded statistics -- most of the UNet's ResBlock norms -- is computed as before in both builds.
+ * Operands of the whole GroupNorm family (this call, _stats, _apply, _apply_partials, _finalize_partials, _cat): x / x1 / x2 / y 16-byte aligned
+ * and dense, C (C1, C2) % 8 == 0 (16-byte loads and stores of 8-channel chunks); gamma, beta, sums, partial(_ws), stats_ws 4-byte aligned
+ * (floats); else VK_EINVAL. */
 int vk_groupnorm_silu_bf16(const void* x, void* y, const float* gamma, const float* beta, float* stats_ws,
                            int32_t n_img, int32_t S, int32_t C, int32_t frames_per_group, float eps, int32_t silu,
                            void* stream);
@@ -303,14 +331,16 @@ int vk_groupnorm_apply_partials_bf16(const void* x, void* y, const float* gamma,
 /* LayerNorm over C of x[rows][C] (+ optional per-image pre-add vector):  u = x + addvec[row / rows_per_vec];
  * if sum_out: sum_out = u (bf16);  y = LN(u)*gamma + beta.
  * Replaces nn.LayerNorm at attention.py:514-524 (norm1-3) and video_attention.py:119-137 (norm_in, norm1-3),
- * fused with the `x_mix = x + emb` add of video_attention.py:283-284. */
+ * fused with the `x_mix = x + emb` add of video_attention.py:283-284.
+ * Operands: x, y, sum_out 16-byte aligned and dense, C % 8 == 0 (16-byte accesses); gamma, beta, addvec 4-byte aligned (floats); else VK_EINVAL. */
 int vk_layernorm_bf16(const void* x, void* y, void* sum_out, const float* gamma, const float* beta,
                       const float* addvec, int32_t rows, int32_t C, int32_t rows_per_vec, int32_t ldv, float eps,
                       void* stream);
 
 /* Row sums for a LayerNorm folded into the consumer GEMM (VkGemmDesc.ln_stats with ln_parts = 1) when the tensor was not produced
  * by a GEMM epilogue on this rank (pixel-sharded temporal block after the all-to-all): stats[row] = (sum_c x, sum_c x^2) of
- * x[rows][ldx] (first C columns), fixed order. Read-only pass: half the traffic of vk_layernorm_bf16. C % 8 == 0, C <= 1536. */
+ * x[rows][ldx] (first C columns), fixed order. Read-only pass: half the traffic of vk_layernorm_bf16. C % 8 == 0, C <= 1536.
+ * Operands: x 16-byte aligned, ldx % 8 (16-byte loads); stats 8-byte aligned (float2 stores); else VK_EINVAL. */
 int vk_rowstats_bf16(const void* x, float* stats, int32_t rows, int32_t C, int64_t ldx, void* stream);
 
 /* vk_groupnorm_silu_bf16 over the channel concat [x1 | x2] (C1 + C2 channels, both token-major, C1 % 8 == C2 % 8 == 0) without
@@ -321,16 +351,19 @@ int vk_groupnorm_silu_cat_bf16(const void* x1, const void* x2, void* y, const fl
                                void* stream);
 
 /* ------------------------------------------------------------------ elementwise / layout */
-/* out[m][0:C1] = a[m][:], out[m][C1:C1+C2] = b[m][:]  (channel concat of the UNet skip: video_model.py:493) */
+/* out[m][0:C1] = a[m][:], out[m][C1:C1+C2] = b[m][:]  (channel concat of the UNet skip: video_model.py:493)
+ * Operands: a, b, out 16-byte aligned and dense, C1 % 8 == C2 % 8 == 0 (16-byte chunks); else VK_EINVAL. */
 int vk_concat_channels_bf16(const void* a, const void* b, void* out, int64_t rows, int32_t C1, int32_t C2, void* stream);
 
-/* NCHW float (f32) -> token-major bf16 with the channel dim zero-padded to Cpad (UNet entry; video_model.py:473) */
+/* NCHW float (f32) -> token-major bf16 with the channel dim zero-padded to Cpad (UNet entry; video_model.py:473)
+ * Operands: x 4-byte aligned (floats); out 16-byte aligned, Cpad % 8 == 0 (16-byte stores); else VK_EINVAL. */
 int vk_nchw_to_tokens_bf16(const float* x, void* out, int32_t n_img, int32_t C, int32_t HW, int32_t Cpad, void* stream);
-/* token-major f32 [n_img][HW][ldx] (first C columns) -> NCHW f32 (UNet exit; video_model.py:502-503) */
+/* token-major f32 [n_img][HW][ldx] (first C columns) -> NCHW f32 (UNet exit; video_model.py:502-503). Operands: x, out 4-byte aligned (floats). */
 int vk_tokens_to_nchw_f32(const float* x, float* out, int32_t n_img, int32_t C, int32_t HW, int32_t ldx, void* stream);
 
 /* sinusoidal timestep embedding: out[n][0:half]=cos(t[n]*f_j), out[n][half:]=sin(t[n]*f_j), f_j=exp(-ln(max_period)*j/half)
- * (vwm/modules/diffusionmodules/util.py:141-165); bf16 output feeds the embedding MLPs */
+ * (vwm/modules/diffusionmodules/util.py:141-165); bf16 output feeds the embedding MLPs.
+ * Operands (both forms, and vk_emb_combine below): every pointer aligned to its element (fp32: 4 bytes, 16-bit: 2); else VK_EINVAL. */
 int vk_timestep_embedding_bf16(const float* t, void* out, int32_t n, int32_t dim, float max_period, void* stream);
 /* The same sinusoid in fp32: ConcatTimestepEmbedderND of the conditioner (vwm/modules/encoders/modules.py:402-425 over openaimodel.py Timestep). */
 int vk_timestep_embedding_f32(const float* t, float* out, int32_t n, int32_t dim, float max_period, void* stream);
@@ -350,7 +383,9 @@ int vk_cast_f32_to_bf16(const float* x, void* y, int64_t count, void* stream);
  * x, cond_frame: f32 NCHW [T][4][HW]; mask: f32 [T].
  * vk_sampler_prepare: xr = x*(1-mask) + cond_frame*mask (written back to x when replace != 0) and builds the
  *   CFG-doubled UNet input in token-major bf16 [2T][HW][Cpad]: ch 0-3 = xr * c_in, ch 4-7 = concat latent
- *   (uncond half: concat_uc, cond half: concat_c; f32 NCHW [T][4][HW]), remaining channels 0. */
+ *   (uncond half: concat_uc, cond half: concat_c; f32 NCHW [T][4][HW]), remaining channels 0.
+ * Operands: the fp32 tensors 4-byte aligned; net_in 16-byte aligned, Cpad % 8 == 0 (16-byte stores); vk_sampler_update: x, net_out, scale 4-byte
+ * aligned (floats). Else VK_EINVAL. */
 int vk_sampler_prepare(float* x, const float* cond_frame, const float* mask, const float* concat_uc,
                        const float* concat_c, void* net_in, int32_t T, int32_t HW, int32_t Cpad, float c_in,
                        int32_t replace, void* stream);

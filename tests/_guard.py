@@ -17,6 +17,12 @@ tile any kernel variant owns. The front guard is a multiple of 256 B, so the ten
 as without guards); the back guard starts at the first byte after the tensor. All guard memory is allocated memory: a wrong kernel damages a
 guard, never an unmapped page.
 
+Skewed and strided arenas (the operand contract of include/vista_hip.h has a misaligned side and a padded-row side of every switch): put / embed /
+scratch / empty take `skew`, bytes between the aligned start and the tensor's first byte, and `ld`, the row stride in elements (rows = all dims
+but the last, flattened; ld >= the last dim). The arena is then [front guard | skew | row 0 | gap | row 1 | gap ... | last row | back guard]: the
+skew bytes and the gaps between rows are poison and verify() checks them as guard memory -- a store whose address was rounded down lands in the
+skew, a store of a whole ld-wide row in a gap. The tensor is a view of exactly the rows: data_ptr() % 256 == skew % 256, stride(-2) == ld.
+
 No conftest, no hook in ops.py: the proxy forwards every attribute to torch except the factories through which ops.py creates kernel-visible
 memory. What ops.py creates another way (the `colsum` of a LayerNorm fold, the operand of pack_ff_out) is re-homed by rehome_pack(), which the
 cases call on such packs. The per-stream split-K workspace ops.py caches is dropped when a context is entered and left, so each context allocates
@@ -42,26 +48,58 @@ class Arena:
     """[front guard | tensor | back guard] in one uint8 allocation. role: "empty" (poisoned interior), "zeros", "ones", "full" (outputs and
     workspaces: guards checked), "input" (guards checked and the interior compared with `saved`), "scratch" (a copy the kernel may write)."""
 
-    def __init__(self, shape, dtype, device, role, label):
+    def __init__(self, shape, dtype, device, role, label, skew=0, ld=None):
         self.shape, self.dtype, self.role, self.label = tuple(shape), dtype, role, label
-        item = torch.empty((), dtype=dtype).element_size()
+        item = self.item = torch.empty((), dtype=dtype).element_size()
         n = 1
         for s in self.shape:
             n *= s
-        self.nbytes = n * item
+        self.cols = self.shape[-1] if self.shape else 1
+        self.rows = n // self.cols if self.cols else 0
+        self.skew, self.ld = int(skew), (self.cols if ld is None else int(ld))
+        if self.skew < 0 or self.skew % item or self.ld < self.cols or (self.ld != self.cols and len(self.shape) < 2):
+            raise ValueError(f"arena of {self.shape} {dtype}: skew {skew} must be a non-negative multiple of the element size, ld {ld} >= the last dim")
+        self.strided = self.ld != self.cols and self.rows > 1
+        # the bytes from the tensor's first to its last: dense, or `rows` rows that start ld elements apart
+        self.nbytes = ((self.rows - 1) * self.ld + self.cols) * item if self.strided else n * item
         self.guard = guard_bytes(self.shape, item)
-        self.base = torch.empty(2 * self.guard + self.nbytes, dtype=torch.uint8, device=device)
+        self.start = self.guard + self.skew
+        self.base = torch.empty(self.start + self.nbytes + self.guard, dtype=torch.uint8, device=device)
         self.base.fill_(POISON)
         self.saved = None
 
     def interior(self):
-        return self.base[self.guard:self.guard + self.nbytes]
+        """The tensor's own bytes: flat (dense), or (rows, row bytes) without the gaps (strided)."""
+        if self.strided:
+            return self.base.as_strided((self.rows, self.cols * self.item), (self.ld * self.item, 1), self.start)
+        return self.base[self.start:self.start + self.nbytes]
 
     def tensor(self):
+        if self.strided:
+            strides, acc = [1], self.ld
+            for s in reversed(self.shape[1:-1]):
+                strides.insert(0, acc)
+                acc *= s
+            strides.insert(0, acc)
+            flat = self.base[self.start:self.start + self.nbytes].view(self.dtype)
+            return flat.as_strided(self.shape, strides, flat.storage_offset())   # (as_strided counts from the storage's start)
         return self.interior().view(self.dtype).view(self.shape)
 
     def sides(self):
-        return (("front", self.base[:self.guard]), ("back", self.base[self.guard + self.nbytes:]))
+        """Every run of guard bytes: (name, bytes, position of byte k of it in words). The front guard includes the skew."""
+        out = [("front", self.base[:self.start]), ("back", self.base[self.start + self.nbytes:])]
+        if self.strided:
+            out.append(("gap", self.base.as_strided((self.rows - 1, (self.ld - self.cols) * self.item), (self.ld * self.item, 1),
+                                                    self.start + self.cols * self.item)))
+        return tuple(out)
+
+    def where(self, side, k):
+        if side == "front":
+            return f"{self.start - k} bytes before its first byte"
+        if side == "back":
+            return f"{k} bytes past its last byte"
+        per = (self.ld - self.cols) * self.item
+        return f"{k % per} bytes past the end of row {k // per}"
 
     def __repr__(self):
         return f"{self.label} {self.shape} {self.dtype}"
@@ -94,8 +132,8 @@ class Session:
         self.proxy = _TorchProxy(self)
 
     # ---- allocation ----
-    def _new(self, shape, dtype, device, role, label):
-        a = Arena(shape, dtype, device, role, label)
+    def _new(self, shape, dtype, device, role, label, skew=0, ld=None):
+        a = Arena(shape, dtype, device, role, label, skew, ld)
         self.arenas.append(a)
         self._storages[a.base.untyped_storage().data_ptr()] = a
         return a
@@ -118,14 +156,19 @@ class Session:
             t.fill_(args[1] if len(args) > 1 else kw["fill_value"])
         return t
 
-    def put(self, t, device="cuda", writable=False, label="input"):
-        """A copy of t (values, shape and dtype; dense) inside an arena on `device`. Unless writable, verify() holds it bitwise unchanged."""
-        a = self._new(t.shape, t.dtype, device, "scratch" if writable else "input", label)
+    def put(self, t, device="cuda", writable=False, label="input", skew=0, ld=None):
+        """A copy of t (values, shape and dtype; dense, or skewed / strided: module docstring) inside an arena on `device`. Unless writable,
+        verify() holds it bitwise unchanged."""
+        a = self._new(t.shape, t.dtype, device, "scratch" if writable else "input", label, skew, ld)
         out = a.tensor()
         out.copy_(t)
         if not writable:
             a.saved = a.interior().clone()
         return out
+
+    def empty(self, shape, dtype, device="cuda", skew=0, ld=None, label="out"):
+        """A poisoned output at a chosen alignment and row stride: what ops.py's own torch.empty cannot be asked for."""
+        return self._new(shape, dtype, device, "empty", label, skew, ld).tensor()
 
     def owns(self, t):
         return t.untyped_storage().data_ptr() in self._storages
@@ -137,13 +180,12 @@ class Session:
         fails = []
         for a in self.arenas:
             for side, g in a.sides():
-                bad = g != POISON
+                bad = (g != POISON).reshape(-1)
                 if bool(bad.any()):
                     k = int(bad.nonzero()[0])
-                    where = f"{a.guard - k} bytes before its first byte" if side == "front" else f"{k} bytes past its last byte"
-                    fails.append(f"{a}: {side} guard damaged, first damaged byte {where} ({int(bad.sum())} of {a.guard} guard bytes changed)")
+                    fails.append(f"{a}: {side} guard damaged, first damaged byte {a.where(side, k)} ({int(bad.sum())} of {bad.numel()} guard bytes changed)")
             if a.saved is not None and not torch.equal(a.interior(), a.saved):
-                k = int((a.interior() != a.saved).nonzero()[0])
+                k = int((a.interior() != a.saved).reshape(-1).nonzero()[0])   # (strided: counted over the rows' own bytes, gaps left out)
                 fails.append(f"{a}: the kernel modified an input it does not own, first at byte {k}")
         new = self.arenas[self._counted:]
         self._counted = len(self.arenas)
@@ -205,21 +247,32 @@ def _need_active(what):
     return _ACTIVE
 
 
-def embed(inputs, device="cuda"):
-    """to_device with arenas: every tensor of a case's inputs copied into an arena of its own on `device`; views made later stay views of it."""
+def embed(inputs, device="cuda", layout=None):
+    """to_device with arenas: every tensor of a case's inputs copied into an arena of its own on `device`; views made later stay views of it.
+    layout: operand name -> (skew bytes, ld elements or None) for the operands that are to sit off the allocator's alignment / in padded rows."""
     s = _need_active("embed()")
-    return inputs.__class__({k: (s.put(v, device, label=f"input {k}") if torch.is_tensor(v) else v) for k, v in inputs.items()})
+    lay = lambda k: dict(zip(("skew", "ld"), (layout or {}).get(k, (0, None))))   # noqa: E731
+    return inputs.__class__({k: (s.put(v, device, label=f"input {k}", **lay(k)) if torch.is_tensor(v) else v) for k, v in inputs.items()})
 
 
-def put(t, device="cuda", label="input"):
-    """One tensor into an arena on `device`, held unchanged by verify(); outside a guarded context: t.to(device)."""
-    return _ACTIVE.put(t, device, label=label) if _ACTIVE is not None else t.to(device)
+def put(t, device="cuda", label="input", skew=0, ld=None):
+    """One tensor into an arena on `device`, held unchanged by verify(); outside a guarded context: t.to(device) (no skew / ld there)."""
+    if _ACTIVE is None and (skew or ld is not None):
+        raise RuntimeError("put(skew= / ld=) outside guarded(ops)")
+    return _ACTIVE.put(t, device, label=label, skew=skew, ld=ld) if _ACTIVE is not None else t.to(device)
 
 
-def scratch(t, label="scratch"):
+def scratch(t, label="scratch", skew=0, ld=None):
     """A copy of t that the entry point under test is DECLARED to write (vk_sampler_prepare with `replace`, vk_sampler_update's x, the `partial`
     of vk_groupnorm_finalize_partials, out == in of the stroke overlay): guards checked, contents not held. Outside a context: t.clone()."""
-    return _ACTIVE.put(t, t.device, writable=True, label=label) if _ACTIVE is not None else t.clone()
+    if _ACTIVE is None and (skew or ld is not None):
+        raise RuntimeError("scratch(skew= / ld=) outside guarded(ops)")
+    return _ACTIVE.put(t, t.device, writable=True, label=label, skew=skew, ld=ld) if _ACTIVE is not None else t.clone()
+
+
+def empty(shape, dtype, device="cuda", skew=0, ld=None, label="out"):
+    """A poisoned output tensor at `skew` bytes past the aligned start with rows `ld` elements apart, for an ops.* call's out= argument."""
+    return _need_active("empty()").empty(shape, dtype, device, skew, ld, label)
 
 
 def rehome_pack(pw):

@@ -15,6 +15,14 @@ The GPU modules run every case on poisoned outputs inside guard bands (tests/_gu
 arena copies, the ops.* calls allocate arenas, and run() re-homes what a pack builds outside the allocation factories (rehome_pack: the colsum
 of a LayerNorm fold, pack_ff_out) and takes a scratch copy of the one operand an entry point is declared to write (scratch).
 
+Operand layouts (the `operand_*` cases; include/vista_hip.h: the operand contract): the supported NARROW side of every alignment switch of the GEMM
+family -- out / res1 / res2 at 8 bytes past a 16-byte boundary or in rows of N + 4 elements, an fp32 out in rows of N + 4, activations off the
+128-byte line -- at M = 260 (one full 256-row tile + a ragged one, a ragged third 128-row tile), N = 320, K = 192 (three K-steps). One operand
+varies at a time, everything else keeps the allocator's alignment; the varied input sits in a skewed / strided arena (Case.layout), the varied output
+in one of its own (_guard.empty), so a store rounded down to 16 bytes or a row stored ld wide damages poison. Bounds A / F32 as everywhere, nothing
+adopted. Each run also makes the aligned call and prints whether the two are bitwise equal (asserted where the sources state it: the same tile
+variant, or variants 4 and 7), and asserts with vk_gemm_tile_choice on the launch's own descriptor which side of the switch ran.
+
 Bounds (derived, never taken from the code under test):
   A   single-rounding kernels. With u = 2^-11 (fp16; 2^-8 for a bf16 output) BOTH
         1. |out - ref| <= 1.25 u |ref| + (u / 4) rms(ref) for EVERY element (round-to-nearest is within u relative of the fp32 value; fp32
@@ -31,12 +39,14 @@ Bounds (derived, never taken from the code under test):
 A LayerNorm folded into a weight pack multiplies gamma into the weight BEFORE the pack rounds it to the storage type, so the reference of a folded
 case uses that rounded product (recomputed here with the pack's own fp32 arithmetic): "the same values" are the values the kernel is handed.
 """
+import ctypes
 import math
 import types
 
 import torch
 import torch.nn.functional as F
 
+from tests import _guard
 from tests._guard import rehome_pack, scratch
 
 F16, BF16, F32, F64 = torch.float16, torch.bfloat16, torch.float32, torch.float64
@@ -253,11 +263,12 @@ def conv_t3_ref(x, w, b, B, T, S):
 class Case:
     """kbreak(inputs) -> inputs with the last 32 of K dropped from the weight (E.3; GEMM / conv cases). rows: the output rows of output 0 are
     its first dims flattened, except trans=True (linear_vt: (n, N, S), rows = (n, S)). cfgs: the forced tile variants of a tiles=True case
-    (default: all of TILE_CFGS; conv3d: 0-3, as tests/test_vae_gpu.py)."""
+    (default: all of TILE_CFGS; conv3d: 0-3, as tests/test_vae_gpu.py). layout: input name -> (skew bytes, ld elements or None), honoured by
+    tests/_guard.py: embed() -- that operand sits `skew` bytes past the allocator's alignment in rows `ld` elements apart, poison in between."""
 
-    def __init__(self, name, build, ref, run, specs, tiles=False, kbreak=None, trans=False, group="gemm", cfgs=None, dround=None):
+    def __init__(self, name, build, ref, run, specs, tiles=False, kbreak=None, trans=False, group="gemm", cfgs=None, dround=None, layout=None):
         self.name, self.build, self.ref, self.run, self.specs = name, build, ref, run, specs
-        self.tiles, self.kbreak, self.trans, self.group, self.dround = tiles, kbreak, trans, group, dround
+        self.tiles, self.kbreak, self.trans, self.group, self.dround, self.layout = tiles, kbreak, trans, group, dround, dict(layout or {})
         self.cfgs = (cfgs or TILE_CFGS) if tiles else (0,)   # the forced block tiles the GPU module runs the case under
 
     def __repr__(self):
@@ -279,6 +290,41 @@ def drop_k(key="w", n=32):
         j[key] = w
         return j
     return f
+
+
+def planned(ops, fn):
+    """fn() with vk_gemm_tile_choice of every vk_gemm_bf16 launch it makes, asked about the launch's own descriptor -> (result, [variant * 16 + K slices])."""
+    asked, gemm = [], ops._gemm
+
+    def recording(desc, emit_stats=False, device=None):
+        ops._prepare(desc)
+        if emit_stats:   # planned as the launch will be: with a row-sum buffer (ops._gemm sets the real one; any 8-byte aligned address answers alike)
+            desc.rowstat_out = desc.Wt
+        asked.append(ops._lib.load().vk_gemm_tile_choice(ctypes.byref(desc)))
+        if emit_stats:
+            desc.rowstat_out = None
+        return gemm(desc, emit_stats, device)
+    ops._gemm = recording
+    try:
+        return fn(), asked
+    finally:
+        ops._gemm = gemm
+
+
+def same_bits_stated(a, b):
+    """Do the sources state that launches planned as a and b (variant * 16 + K slices) store the same bits? The same variant and K slices (the general
+    epilogue is bitwise the LDS-staged one: csrc/gemm_common.h), or the pipelined kernel against the sixteen-wave one (include/vista_hip.h: 7 == 4)."""
+    return a % 16 == b % 16 and (a // 16 == b // 16 or {a // 16, b // 16} == {4, 7})
+
+
+def stats_follow_the_output(st, out):
+    """RowStats slabs summed over parts against float64 (sum, sum of squares) of the kernel's own 16-bit output rows: the rule of
+    tests/_parity_bodies.py: check_stats. -> worst error in units of the tolerance."""
+    o = out.double()
+    got = st.t.sum(0).double()
+    ref = torch.stack([o.sum(1), o.pow(2).sum(1)], 1)
+    tol = 2e-5 * torch.stack([o.abs().sum(1), o.pow(2).sum(1)], 1) + 1e-6
+    return ((got - ref).abs() / tol).max().item()
 
 
 def last_tile_rows(M, tile=128):
@@ -1329,6 +1375,155 @@ def make_cases(st):
 
         _gelu_mlp(257, 5120, 1280)
         _gelu_mlp(100, 64, 128)
+
+    # ------------------------------------------------------------------------------------------------ operand layouts: the narrow side of every switch
+    def _operand_case(name, build, ref, call, layout=None, out_lay=None, out_shape=None, f32=False, narrow=True, cfgs=None, bitwise="stated", want=None,
+                      kbreak=None):
+        """call(ops, i, out) -> the ops.* result (out=None: the wrapper allocates, aligned). layout: input name -> (skew, ld) (Case.layout);
+        out_lay: (skew, ld) of an output arena of out_shape. narrow: the layout knocks the launch off the pipelined kernel (forced 7 must not answer 7).
+        bitwise: "stated" = asserted where same_bits_stated, "always" = asserted (the source promises it), None = printed only.
+        want: forced variant -> (plan of the laid-out launch, plan of the aligned one), asserted."""
+        layout = dict(layout or {})
+
+        def run(ops, i):
+            dev = i.x.device
+            line = 256 if dev.type == "cuda" else 16   # (the GPU allocator hands out 256-byte aligned blocks; the CPU dry runs of the harness see 64)
+            for k, (skew, ld) in layout.items():   # which side of a switch runs is a pure function of these
+                assert i[k].data_ptr() % line == skew % line and (ld is None or i[k].stride(-2) == ld) and i[k].stride(-1) == 1, (k, i[k].data_ptr() % 256, i[k].stride())
+            out = None
+            if out_lay is not None:
+                out = _guard.empty(out_shape, F32 if f32 else ST, dev, skew=out_lay[0], ld=out_lay[1], label=f"out of {name}")
+                assert out.data_ptr() % line == out_lay[0] % line and out.stride() == (out_lay[1] or out_shape[1], 1), (out.data_ptr() % 256, out.stride())
+            got, asked = planned(ops, lambda: call(ops, i, out))
+            twin = I({k: (_guard.put(v.contiguous(), dev, label=f"aligned {k}") if k in layout else v) for k, v in i.items()})
+            assert all(v.data_ptr() % line == 0 for v in twin.values() if torch.is_tensor(v))
+            base, asked0 = planned(ops, lambda: call(ops, twin, None))
+            stats = None
+            if isinstance(got, tuple):
+                (got, stats), (base, stats0) = got, base
+            equal = got.shape == base.shape and torch.equal(got, base)
+            differing = int((got != base).sum()) if got.shape == base.shape else -1
+            apart = ((got.double() - base.double()).abs() / base.double().abs().clamp_min(1e-30)).max().item() if differing > 0 else 0.0
+            print(f"OPERANDS {name} {'fp16' if ST is F16 else 'bf16'} cfg{ops.TILE_CFG} plan={asked} aligned_plan={asked0} bitwise_the_aligned_call={equal}"
+                  f" differing={differing}/{got.numel()} worst_relative_gap={apart:.3g}")
+            assert all(c > 0 for c in asked + asked0), (asked, asked0)
+            if narrow and ops.TILE_CFG == 7:
+                assert all(c // 16 not in (6, 7) for c in asked), f"{name}: planned {asked} on a kernel that carries only the 16-byte epilogue"
+            if want is not None and ops.TILE_CFG in want:
+                assert (asked[-1], asked0[-1]) == want[ops.TILE_CFG], (asked, asked0, want[ops.TILE_CFG])
+            if bitwise == "always" or (bitwise == "stated" and len(asked) == len(asked0) and all(same_bits_stated(a, b) for a, b in zip(asked, asked0))):
+                assert equal, f"{name}: {int((got != base).sum())} elements differ from the aligned call (plans {asked} / {asked0})"
+            if stats is not None:
+                worst = stats_follow_the_output(stats, got)
+                print(f"OPERANDS {name} rowstats worst/tol={worst:.3g} slabs_bitwise_the_aligned_call={stats.t.shape == stats0.t.shape and torch.equal(stats.t, stats0.t)}")
+                assert worst <= 1.0 and stats.M == got.shape[0], worst
+            return [got]
+        add(name, build, ref, run, [("F32",) if f32 else ("A", ST)], tiles=True, kbreak=kbreak or drop_k(), cfgs=cfgs, layout=layout)
+
+
+    def _operand_cases():
+        M, N, K, rpv = 260, 320, 192, 130       # (rows_per_vec >= 128: a 256-row tile spans at most 3 images, so the ALIGNED call stays on the staged epilogue)
+        SK, LD = 8, N + 4                      # 8 bytes past a 16-byte boundary; rows of N + 4 elements: every second row 8 bytes off
+
+        def build():
+            g = G(61)
+            return I(x=r16(g, M, K), w=r16(g, N, K, scale=K ** -0.5), b=r32(g, N), r1=r16(g, M, N), r2=r16(g, M, N), rv=r32(g, M // rpv, N), rv2=r32(g, M // rpv, N))
+
+        def y(i):
+            return d(i.x) @ d(i.w).t() + d(i.b)
+
+        def plain(ops, i, out):
+            return ops.linear(i.x, ops.pack_linear(i.w, i.b), out=out)
+
+        def with_res1(ops, i, out):
+            return ops.linear(i.x, ops.pack_linear(i.w, i.b), res1=i.r1, out=out)
+
+        def with_res2(ops, i, out):
+            return ops.linear(i.x, ops.pack_linear(i.w, i.b), res2=i.r2, alpha=0.3, beta=0.7, out=out)
+
+        def full(ops, i, out):
+            return ops.linear(i.x, ops.pack_linear(i.w, i.b), rowvec=i.rv, rows_per_vec=rpv, res1=i.r1, res2=i.r2, alpha=0.3, beta=0.7, rowvec2=i.rv2, out=out)
+
+        def full_ref(i):
+            return [0.3 * (y(i) + d(i.rv).repeat_interleave(rpv, 0) + d(i.r1)) + 0.7 * (d(i.r2) + d(i.rv2).repeat_interleave(rpv, 0))]
+        seven = {7: (4 * 16 + 1, 7 * 16 + 1)}   # the pipelined kernel declines the narrow operand: the sixteen-wave kernel, general epilogue
+        _operand_case("operand_out_skew8", build, lambda i: [y(i)], plain, out_lay=(SK, None), out_shape=(M, N), want=seven)
+        _operand_case("operand_out_ldc_plus4", build, lambda i: [y(i)], plain, out_lay=(0, LD), out_shape=(M, N), want=seven)
+        _operand_case("operand_res1_skew8", build, lambda i: [y(i) + d(i.r1)], with_res1, layout={"r1": (SK, None)}, want=seven)
+        _operand_case("operand_res1_ld_plus4", build, lambda i: [y(i) + d(i.r1)], with_res1, layout={"r1": (0, LD)}, want=seven)
+        _operand_case("operand_res2_skew8", build, lambda i: [0.3 * y(i) + 0.7 * d(i.r2)], with_res2, layout={"r2": (SK, None)}, want=seven)
+        _operand_case("operand_res2_ld_plus4", build, lambda i: [0.3 * y(i) + 0.7 * d(i.r2)], with_res2, layout={"r2": (0, LD)}, want=seven)
+        # (this case found the two epilogue bodies one fp32 bit apart in the fp16 build -- the compiler's contraction of alpha * u + beta * t, per
+        #  instantiation: 13 / 14 of the 83200 outputs one fp16 ulp apart; the blend is now written with an explicit fmaf in every body, csrc/gemm_common.h)
+        _operand_case("operand_full_epilogue_out_skew8", build, full_ref, full, out_lay=(SK, None), out_shape=(M, N), want=seven)
+        _operand_case("operand_emit_stats_out_skew8", build, lambda i: [y(i)], lambda ops, i, out: ops.linear(i.x, ops.pack_linear(i.w, i.b), emit_stats=True, out=out),
+                      out_lay=(SK, None), out_shape=(M, N))
+        _operand_case("operand_f32_out_ldc_plus4", build, lambda i: [y(i)], lambda ops, i, out: ops.linear(i.x, ops.pack_linear(i.w, i.b), out_f32=True, out=out),
+                      out_lay=(0, LD), out_shape=(M, N), f32=True, narrow=False)
+        _operand_case("operand_act_gelu_out_skew8", build, lambda i: [gelu64(y(i))], lambda ops, i, out: ops.linear(i.x, ops.pack_linear(i.w, i.b), act="gelu", out=out),
+                      out_lay=(SK, None), out_shape=(M, N), want=seven)
+        # the L2-prefetch switch of the pipelined kernel (csrc/gemm_pipe.hip: A 128-byte aligned with lda % 64 == 0, K >= 3 K-steps, one round of tiles):
+        # the activations 16 bytes off the line in rows of K + 8 elements against the aligned call -- "bitwise the same results either way"
+        _operand_case("operand_a_off_the_128_byte_line", build, lambda i: [y(i)], plain, layout={"x": (16, K + 8)}, narrow=False, bitwise="always",
+                      want={7: (7 * 16 + 1, 7 * 16 + 1)})
+
+        # LayerNorm-folded q|k|v and GEGLU at width 320 (N = 960 / 2560: whole 320-column tiles, so that the pipelined kernel is what the operand loses)
+        C = 320
+
+        def build_c(geglu):
+            def build():
+                g = G(62 + geglu)
+                return I(x=r16(g, M, C, shift=0.3), w=r16(g, (8 if geglu else 3) * C, C, scale=C ** -0.5), b=r32(g, (8 if geglu else 3) * C),
+                         gamma=r32(g, C, scale=0.2, shift=1.0), beta=r32(g, C, scale=0.3))
+            return build
+
+        def qkv(ops, i, out):
+            return ops.linear(i.x, rehome_pack(ops.pack_linear(i.w, i.b, ln=Norm(i.gamma, i.beta))), ln=ops.rowstats(i.x), out=out)
+
+        def geglu_ref(i):
+            a, gt = (d(i.x) @ d(i.w).t() + d(i.b)).chunk(2, dim=-1)
+            return [a * gelu64(gt)]
+        _operand_case("operand_qkv_lnfold_out_skew8", build_c(0), lambda i: [ln_fold_ref(i.x, i.w, i.b, i.gamma, i.beta)], qkv, out_lay=(SK, None), out_shape=(M, 3 * C))
+        _operand_case("operand_geglu_out_skew8", build_c(1), geglu_ref, lambda ops, i, out: ops.linear(i.x, ops.pack_geglu(i.w, i.b), out=out),
+                      out_lay=(SK, None), out_shape=(M, 4 * C))
+
+        # the implicit-GEMM convolutions: out and res1 both 8 bytes off
+        n, H, W, Cin = 2, 9, 16, 64
+
+        def build_conv():
+            g = G(64)
+            return I(x=r16(g, n, H * W, Cin), w=r16(g, N, Cin, 3, 3, scale=(9 * Cin) ** -0.5), b=r32(g, N), r1=r16(g, n * H * W, N))
+
+        def conv(ops, i, out):
+            return ops.conv3x3(i.x, ops.pack_conv3x3(i.w, i.b), n, H, W, res1=i.r1, out=out)[0].view(n * H * W, N)
+        _operand_case("operand_conv3x3_out_res1_skew8", build_conv, lambda i: [conv3x3_ref(i.x, i.w, i.b, n, H, W).reshape(n * H * W, N) + d(i.r1)], conv,
+                      layout={"r1": (SK, None)}, out_lay=(SK, None), out_shape=(n * H * W, N))
+        B, T, S = 1, 3, 144
+
+        def build_t3():
+            g = G(65)
+            return I(x=r16(g, B * T, S, Cin), w=r16(g, N, Cin, 3, 1, 1, scale=(3 * Cin) ** -0.5), b=r32(g, N), r1=r16(g, B * T * S, N))
+
+        def conv_t(ops, i, out):
+            return ops.conv_t3(i.x, ops.pack_conv_t3(i.w, i.b), T, S, res1=i.r1, out=out).view(B * T * S, N)
+        def drop_centre_tap(i):   # (one clip: the last tile's rows are the last frame, whose tap 2 reads zero padding -- drop 32 of K from the centre tap)
+            j = I(i)
+            j["w"] = i.w.clone()
+            j["w"][:, -32:, 1] = 0
+            return j
+        _operand_case("operand_conv_t3_out_res1_skew8", build_t3, lambda i: [conv_t3_ref(i.x, i.w, i.b, B, T, S).reshape(B * T * S, N) + d(i.r1)], conv_t,
+                      layout={"r1": (SK, None)}, out_lay=(SK, None), out_shape=(B * T * S, N), kbreak=drop_centre_tap)
+
+        # the streaming kernel's decline at its smallest forced shape (K = 320, N = 320): A 16-byte aligned but off the 128-byte line, out 8 bytes off --
+        # forced variant 6 must fall back to a tiled kernel
+        def build_s():
+            g = G(66)
+            return I(x=r16(g, M, C), w=r16(g, N, C, scale=C ** -0.5), b=r32(g, N))
+        _operand_case("operand_stream_declines_out_skew8", build_s, lambda i: [d(i.x) @ d(i.w).t() + d(i.b)], plain, layout={"x": (16, None)}, out_lay=(SK, None),
+                      out_shape=(M, N), cfgs=(6,), narrow=False, bitwise=None, want={6: (1 * 16 + 1, 6 * 16 + 1)})
+
+
+    _operand_cases()
 
     BY_NAME = {c.name: c for c in CASES}
     assert len(BY_NAME) == len(CASES)

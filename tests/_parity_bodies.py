@@ -54,7 +54,7 @@ def case_under_tile(ops, fc, case, cfg, device="cuda"):
     with _guard.guarded(ops):
         ops.TILE_CFG = cfg
         try:
-            outs = case.run(ops, _guard.embed(i, device))
+            outs = case.run(ops, _guard.embed(i, device, layout=case.layout))
         finally:
             ops.TILE_CFG = 0
         judge(fc, case, outs, refs, f"cfg{cfg}")

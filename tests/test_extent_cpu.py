@@ -3,7 +3,11 @@ stand-ins for a kernel -- out = bf16(1.5 x + 0.25) on a (300, 4) bf16 operand, a
 -- are driven through the very body the GPU modules use (tests/_parity_bodies.py: case_under_tile -> guarded, embed, judge with bound A, verify).
 The correct stand-in passes; one that leaves an element unwritten, stores outside its output, loads past its operand into the result or writes an
 operand it does not own fails, for that reason, and a damaged guard names the right tensor. A stand-in reaches the bytes around a tensor the way
-a kernel does: by address (as_strided on the arena's storage)."""
+a kernel does: by address (as_strided on the arena's storage).
+
+Skewed and strided arenas (tests/_guard.py: skew, ld): the same stand-in on an operand 8 bytes past the aligned start in rows of COLS + 2 elements and
+an output 8 bytes past it in rows of COLS + 4 passes; one that rounds its first store's address down to 16 bytes is caught in the front skew, one
+that stores whole ld-wide rows in a row gap, and a load of a padded operand's gap reaches the result as NaN."""
 import re
 
 import pytest
@@ -36,12 +40,36 @@ def _byte(t, offset):
     return flat[t.storage_offset() * t.element_size() + offset:][:1]
 
 
+SKEW, LD_OUT, LD_IN = 8, COLS + 4, COLS + 2
+LAYOUT_KINDS = ("correct_skewed_and_strided", "rounds_its_store_address_down_to_16_bytes", "stores_a_full_ld_wide_row", "loads_a_full_ld_wide_row")
+
+
 def _standin(kind):
+    laid_out = kind in LAYOUT_KINDS
+
     def run(ops, i):
         aux = ops.torch.empty((7, 64), dtype=F32, device=i.x.device)      # a second, untouched allocation: never the one a failure names
-        out = ops.torch.empty((ROWS, COLS), dtype=BF16, device=i.x.device)
+        if laid_out:
+            out = _guard.empty((ROWS, COLS), BF16, i.x.device, skew=SKEW, ld=LD_OUT)
+            assert out.data_ptr() % 16 == SKEW and out.stride() == (LD_OUT, 1) and i.x.data_ptr() % 16 == SKEW and i.x.stride() == (LD_IN, 1)
+        else:
+            out = ops.torch.empty((ROWS, COLS), dtype=BF16, device=i.x.device)
         aux.fill_(0.0)
         y = (i.x.float() * 1.5 + 0.25).to(BF16)
+        if kind == "rounds_its_store_address_down_to_16_bytes":            # row 0's 8-byte store at (address & ~15): the 8 bytes before the tensor
+            out.copy_(y)
+            out.as_strided((COLS,), (1,), out.storage_offset() - SKEW // 2).copy_(y[0])
+            return [out]
+        if kind == "stores_a_full_ld_wide_row":                            # row 5 stored LD_OUT elements wide: its gap is written
+            out.copy_(y)
+            out.as_strided((LD_OUT,), (1,), out.storage_offset() + 5 * LD_OUT).fill_(0.5)
+            out[5] = y[5]
+            return [out]
+        if kind == "loads_a_full_ld_wide_row":                             # the last column's load one element further: the operand's gap
+            wide = i.x.as_strided((ROWS, COLS + 1), (LD_IN, 1), i.x.storage_offset())
+            out.copy_((wide[:, 1:].float() * 1.5 + 0.25).to(BF16))
+            out[:, :-1] = y[:, :-1]
+            return [out]
         if kind == "skips_last_row":
             out[:-1] = y[:-1]
         elif kind == "skips_one_element":
@@ -68,7 +96,7 @@ def _standin(kind):
 
     def build():
         return fc.I(x=fc.r16(fc.G(77), ROWS, COLS))
-    return fc.Case(f"extent_standin_{kind}", build, lambda i: [fc.d(i.x) * 1.5 + 0.25], run, [("A", BF16)])
+    return fc.Case(f"extent_standin_{kind}", build, lambda i: [fc.d(i.x) * 1.5 + 0.25], run, [("A", BF16)], layout={"x": (SKEW, LD_IN)} if laid_out else None)
 
 
 def _drive(ops, kind):
@@ -103,6 +131,27 @@ def test_a_store_outside_the_output_fails_and_names_it(kind, side, where, ops):
     lines = [ln for ln in msg.splitlines() if "guard damaged" in ln]
     assert len(lines) == 1, msg                              # one tensor, one side: neither the operand nor the other allocation
     assert lines[0].strip().startswith(f"{OUT}: {side} guard damaged") and re.search(where, lines[0]), lines[0]
+
+
+def test_a_correct_standin_on_skewed_and_strided_operands_passes(ops):
+    _drive(ops, "correct_skewed_and_strided")
+
+
+@pytest.mark.parametrize("kind,side,where", [
+    ("rounds_its_store_address_down_to_16_bytes", "front", f"{SKEW} bytes before its first byte \\({SKEW} of"),
+    ("stores_a_full_ld_wide_row", "gap", f"0 bytes past the end of row 5 \\({2 * (LD_OUT - COLS)} of"),
+])
+def test_a_store_into_the_skew_or_a_row_gap_fails_and_names_it(kind, side, where, ops):
+    with pytest.raises(AssertionError) as e:
+        _drive(ops, kind)
+    lines = [ln for ln in str(e.value).splitlines() if "guard damaged" in ln]
+    assert len(lines) == 1, str(e.value)
+    assert lines[0].strip().startswith(f"out ({ROWS}, {COLS}) torch.bfloat16: {side} guard damaged") and re.search(where, lines[0]), lines[0]
+
+
+def test_a_load_of_a_row_gap_reaches_the_result_as_nan(ops):
+    with pytest.raises(AssertionError, match="nonfinite"):
+        _drive(ops, "loads_a_full_ld_wide_row")
 
 
 def test_a_load_past_the_input_reaches_the_result_as_nan(ops):

@@ -893,7 +893,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 
 extern "C" int vk_softmax_rows_f32_bf16(const float* x, void* y, int64_t rows, int32_t cols, int64_t ldx, int64_t ldy, void* stream_) {
     if (!x || !y || rows <= 0 || rows > 0x7fffffffLL || cols <= 0 || (cols & 3) || cols > SM_MAXV * 256 * 4 || (ldx & 3) || (ldy & 3) ||
-        ldx < cols || ldy < cols)
+        ldx < cols || ldy < cols || !aligned_to(x, 16) || !aligned_to(y, 8))   // float4 loads, uint2 stores
         return VK_EINVAL;
     hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream_, x, (uint16_t*)y, cols, (long long)ldx,
                        (long long)ldy);
@@ -1293,6 +1293,7 @@ __global__ __launch_bounds__(64) void attn_small_kernel(const uint16_t* __restri
 extern "C" int vk_attn_small_bf16(const void* qkv, void* o, int32_t n_img, int32_t heads, int32_t S, int32_t D, int32_t ld, int32_t k_off,
                                   int32_t v_off, int32_t ldo, float scale, void* stream_) {
     if (!qkv || !o || n_img <= 0 || heads <= 0 || S <= 0 || (ld % 8) != 0 || (k_off % 8) != 0 || (v_off % 8) != 0 || (ldo % 8) != 0) return VK_EINVAL;
+    if (!aligned_to(qkv, 16) || !aligned_to(o, 16)) return VK_EINVAL;   // 16-byte loads and stores
     const size_t lds = (size_t)S * D * 2 * 2;
     if (lds > 160 * 1024) return VK_EINVAL;
     const dim3 grid((unsigned)(n_img * heads), (unsigned)((S + 63) / 64));
@@ -1316,6 +1317,8 @@ static int attn_spatial_launch(const void* q, const void* k, const void* vt, voi
                                int32_t S, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo, float scale, void* stream_, bool pre = false) {
     if (!q || !k || !vt || !o || n_img <= 0 || heads <= 0 || S <= 0) return VK_EINVAL;
     if ((S % 8) != 0 || (ldq % 8) != 0 || (ldk % 8) != 0 || (ldo % 4) != 0) return VK_EINVAL;
+    // operand contract (include/vista_hip.h): q / k / v (or V^T) arrive in 16-byte pieces; the general kernels store 8 bytes of o at a time
+    if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(vt, 16) || !aligned_to(o, 8)) return VK_EINVAL;
     // long sequences: 256 query rows (8 waves) per workgroup halve the K/V^T stream per FLOP; short ones keep 128 rows so the
     // ragged last q-block wastes less (S = 144, 576 at the deep levels)
     static const float thr = [] { const char* e = getenv("VISTA_ATTN_RESCALE_THR"); return e ? (float)atof(e) : RESCALE_THR; }();  // tuning / A-B
@@ -1391,6 +1394,7 @@ extern "C" int vk_attn_temporal_bf16(const void* qkv, void* o, int32_t B, int32_
                                      int32_t k_off, int32_t v_off, int32_t ldo, float scale, void* stream_) {
     if (!qkv || !o || B <= 0 || T <= 0 || T > 32 || S <= 0 || heads <= 0) return VK_EINVAL;
     if ((ld % 8) != 0 || (k_off % 8) != 0 || (v_off % 8) != 0 || (ldo % 4) != 0) return VK_EINVAL;
+    if (!aligned_to(qkv, 16) || !aligned_to(o, 8)) return VK_EINVAL;   // 16-byte loads; 8-byte stores where o is not 16-byte aligned
     const long long nprob = (long long)B * S * heads;
     const long long want = (nprob + 3) / 4;
     const long long cap = 256LL * 16;  // 16 workgroups per CU keeps plenty of loads in flight

@@ -114,3 +114,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 #define VK_ELAUNCH (-5)
 
 #define VK_CHECK_LAUNCH() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return VK_ELAUNCH; } while (0)
+
+// operand contract (include/vista_hip.h): is `p` a multiple of `a` bytes (a power of two)? NULL is: an absent optional operand is not checked
+static inline bool aligned_to(const void* p, size_t a) { return (((size_t)p) & (a - 1)) == 0; }

@@ -311,27 +311,29 @@ __global__ __launch_bounds__(EW_THREADS) void clip_preprocess_kernel(const float
 
 extern "C" int vk_concat_channels_bf16(const void* a, const void* b, void* out, int64_t rows, int32_t C1, int32_t C2, void* stream) {
     if (!a || !b || !out || rows <= 0 || C1 <= 0 || C2 <= 0 || (C1 % 8) || (C2 % 8)) return VK_EINVAL;
+    if (!aligned_to(a, 16) || !aligned_to(b, 16) || !aligned_to(out, 16)) return VK_EINVAL;   // operand contract (include/vista_hip.h): 16-byte chunks
     EW_LAUNCH(concat_kernel, rows * ((C1 + C2) / 8), (const uint4*)a, (const uint4*)b, (uint4*)out, (long long)rows, C1 / 8, C2 / 8);
 }
 extern "C" int vk_nchw_to_tokens_bf16(const float* x, void* out, int32_t n_img, int32_t C, int32_t HW, int32_t Cpad, void* stream) {
-    if (!x || !out || n_img <= 0 || C <= 0 || HW <= 0 || Cpad < C || (Cpad % 8)) return VK_EINVAL;
+    if (!x || !out || n_img <= 0 || C <= 0 || HW <= 0 || Cpad < C || (Cpad % 8) || !aligned_to(x, 4) || !aligned_to(out, 16)) return VK_EINVAL;
     EW_LAUNCH(nchw_to_tokens_kernel, (long long)n_img * HW * (Cpad / 8), x, (uint4*)out, n_img, C, HW, Cpad);
 }
 extern "C" int vk_tokens_to_nchw_f32(const float* x, float* out, int32_t n_img, int32_t C, int32_t HW, int32_t ldx, void* stream) {
-    if (!x || !out || n_img <= 0 || C <= 0 || HW <= 0 || ldx < C) return VK_EINVAL;
+    if (!x || !out || n_img <= 0 || C <= 0 || HW <= 0 || ldx < C || !aligned_to(x, 4) || !aligned_to(out, 4)) return VK_EINVAL;
     EW_LAUNCH(tokens_to_nchw_kernel, (long long)n_img * C * HW, x, out, n_img, C, HW, ldx);
 }
 extern "C" int vk_timestep_embedding_bf16(const float* t, void* out, int32_t n, int32_t dim, float max_period, void* stream) {
-    if (!t || !out || n <= 0 || dim < 2 || max_period <= 0.f) return VK_EINVAL;
+    if (!t || !out || n <= 0 || dim < 2 || max_period <= 0.f || !aligned_to(t, 4) || !aligned_to(out, 2)) return VK_EINVAL;
     EW_LAUNCH(timestep_embedding_kernel<false>, (long long)n * dim, t, out, n, dim, -logf(max_period));
 }
 extern "C" int vk_timestep_embedding_f32(const float* t, float* out, int32_t n, int32_t dim, float max_period, void* stream) {
-    if (!t || !out || n <= 0 || dim < 2 || max_period <= 0.f) return VK_EINVAL;
+    if (!t || !out || n <= 0 || dim < 2 || max_period <= 0.f || !aligned_to(t, 4) || !aligned_to(out, 4)) return VK_EINVAL;
     EW_LAUNCH(timestep_embedding_kernel<true>, (long long)n * dim, t, (void*)out, n, dim, -logf(max_period));
 }
 extern "C" int vk_emb_combine(const float* a, const float* b, const float* c, const float* mask, float* emb, void* silu_out, int32_t n,
                               int32_t dim, void* stream) {
     if (!b || !emb || n <= 0 || dim <= 0 || (a && !mask)) return VK_EINVAL;
+    if (!aligned_to(a, 4) || !aligned_to(b, 4) || !aligned_to(c, 4) || !aligned_to(mask, 4) || !aligned_to(emb, 4) || !aligned_to(silu_out, 2)) return VK_EINVAL;
     EW_LAUNCH(emb_combine_kernel, (long long)n * dim, a, b, c, mask, emb, (uint16_t*)silu_out, n, dim);
 }
 extern "C" int vk_silu_f32_to_bf16(const float* x, void* y, int64_t count, void* stream) {
@@ -346,12 +348,14 @@ extern "C" int vk_sampler_prepare(float* x, const float* cond_frame, const float
                                   void* net_in, int32_t T, int32_t HW, int32_t Cpad, float c_in, int32_t replace, void* stream) {
     if (!x || !net_in || T <= 0 || HW <= 0 || Cpad < 8 || (Cpad % 8)) return VK_EINVAL;
     if (replace && (!cond_frame || !mask)) return VK_EINVAL;
+    if (!aligned_to(x, 4) || !aligned_to(cond_frame, 4) || !aligned_to(mask, 4) || !aligned_to(concat_uc, 4) || !aligned_to(concat_c, 4) || !aligned_to(net_in, 16))
+        return VK_EINVAL;   // operand contract (include/vista_hip.h): net_in is written 8 channels = 16 bytes at a time
     EW_LAUNCH(sampler_prepare_kernel, (long long)T * HW * (Cpad / 8), x, cond_frame, mask, concat_uc, concat_c, (uint4*)net_in, T, HW, Cpad,
               c_in, replace);
 }
 extern "C" int vk_sampler_update(float* x, const float* net_out, const float* scale, int32_t T, int32_t HW, int32_t ld, float c_out,
                                  float c_skip, float sigma, float sigma_next, void* stream) {
-    if (!x || !net_out || !scale || T <= 0 || HW <= 0 || ld < 4 || sigma == 0.f) return VK_EINVAL;
+    if (!x || !net_out || !scale || T <= 0 || HW <= 0 || ld < 4 || sigma == 0.f || !aligned_to(x, 4) || !aligned_to(net_out, 4) || !aligned_to(scale, 4)) return VK_EINVAL;
     EW_LAUNCH(sampler_update_kernel, (long long)T * 4 * HW, x, net_out, scale, T, HW, ld, c_out, c_skip, sigma, sigma_next);
 }
 extern "C" int vk_denoiser_combine(const float* net, const float* x, const float* c_out, const float* c_skip, float* out, int32_t n_img,

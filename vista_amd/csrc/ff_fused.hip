@@ -372,6 +372,9 @@ inline int ff_validate(const VkGemmDesc* g, const VkGemmDesc* o) {
     if (g->ln_stats && (!g->ln_colsum || (((size_t)g->ln_colsum) & 15) != 0 || g->ln_parts <= 0 || g->ln_parts > 64 || !(g->ln_eps > 0.f))) return VK_EINVAL;
     if ((o->rowvec || o->rowvec2) && o->rows_per_vec <= 0) return VK_EINVAL;
     if (o->rowvec2 && !o->res2) return VK_EINVAL;
+    // operand contract (include/vista_hip.h): both weights arrive by 16-byte LDS-DMA, the row sums as float2, and the out-projection's operands go
+    // through vk_gemm_bf16's LINEAR epilogues
+    if (!aligned_to(g->Wt, 16) || !aligned_to(o->Wt, 16) || !aligned_to(g->ln_stats, 8) || !epilogue_operands_ok(o)) return VK_EINVAL;
     return VK_OK;
 }
 

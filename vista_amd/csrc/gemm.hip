@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const VkGemmDesc p, 
                 const float4 b = *(const float4*)(p.rowvec2 + (size_t)(m / p.rows_per_vec) * p.ldv + n);
                 t[0] += b.x; t[1] += b.y; t[2] += b.z; t[3] += b.w;
             }
-            v[0] += p.beta * t[0]; v[1] += p.beta * t[1]; v[2] += p.beta * t[2]; v[3] += p.beta * t[3];
+            v[0] = fmaf(p.beta, t[0], v[0]); v[1] = fmaf(p.beta, t[1], v[1]); v[2] = fmaf(p.beta, t[2], v[2]); v[3] = fmaf(p.beta, t[3], v[3]);   // (the epilogues' written order: gemm_common.h)
         }
         if (OUT_F32) *(float4*)((float*)p.out + (size_t)m * p.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
         else *(uint2*)((uint16_t*)p.out + (size_t)m * p.ldc + n) = make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
@@ -731,7 +731,7 @@ inline int validate(const VkGemmDesc* d) {
     if (d->alt_cols_from != 0 && (d->alt_cols_from < 0 || (d->alt_cols_from % 32) != 0 || d->alt_cols_from >= d->N || d->epi != EPI_LINEAR || d->out_f32 ||
                                   d->rowstat_out || d->gnstat_out || d->mx8_out))
         return VK_EINVAL;
-    return VK_OK;
+    return operands_ok(d) ? VK_OK : VK_EINVAL;
 }
 
 // validate, normalise the row range into `q`, plan: the whole preamble of every entry point below. rowstat / gnstat: plan as emitting although the

@@ -215,7 +215,7 @@ __device__ __forceinline__ void gemm_epilogue(const VkGemmDesc& p, f32x16_t (&ac
                             t[0] += b.x; t[1] += b.y; t[2] += b.z; t[3] += b.w;
                         }
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] += p.beta * t[e];
+                        for (int e = 0; e < 4; ++e) v[e] = fmaf(p.beta, t[e], v[e]);   // ONE written order of the blend in every body (see the LDS-staged epilogue)
                     }
                     if (OUT_F32) {
                         *(float4*)((float*)p.out + (size_t)m * p.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
@@ -356,7 +356,10 @@ __device__ __forceinline__ void gemm_epilogue(const VkGemmDesc& p, f32x16_t (&ac
 //     (lanes of a half-wave share the address: a broadcast read);
 //   * the residual loads of a row block are issued up front (a ring of `D` fragments ahead of the stores);
 //   * rows past M are clamped for the loads and predicated only at the stores, so the body is branch-free apart from kernel-uniform options.
-// Arithmetic and operation order are those of gemm_epilogue: results are bitwise the same.
+// Arithmetic and operation order are those of gemm_epilogue: results are bitwise the same. The one place where the compiler had a choice -- contracting
+// alpha * u + beta * t into fma(u, alpha, beta * t) or fma(beta, t, alpha * u), decided per instantiation -- is written out in every body (here, in
+// gemm_epilogue and in gemm.hip's splitk_finish_kernel) as fmaf(beta, t, alpha * u) with alpha * u rounded first: left to contraction the fp16 build's
+// two bodies of the full blend came out one fp32 bit apart (tests/_kernel_cases.py: operand_full_epilogue_out_skew8 runs both on one problem).
 constexpr int EPI_NI = 4;  // images a tile's rows may span (256-row tiles: rows_per_vec >= 86)
 __host__ __device__ constexpr int epi_vec_floats(int bn) { return (2 + 2 * EPI_NI) * bn; }  // bias | colsum | EPI_NI x rowvec | EPI_NI x rowvec2
 
@@ -407,6 +410,32 @@ __host__ __device__ inline bool epi_fast_everywhere(const VkGemmDesc& p, int epi
         if ((bm - 1) / p.rows_per_vec + 2 > EPI_NI) return false;   // bm consecutive rows span at most (bm - 1) / rows_per_vec + 2 images
     }
     return true;
+}
+
+// The operand contract (include/vista_hip.h, beside VkGemmDesc): base alignment and leading-dimension multiple of every operand, from the widest
+// access any kernel the plan may pick makes to it. The tiled kernels' general epilogue is the narrow side of every switch (gemm_common.h: `wide`,
+// epi_plan), so its widths are the rule; what only a faster path needs (16-byte out / residual rows, 128-byte activation rows) that path checks itself
+// and declines. NULL optional operands are absent and unchecked.
+// what the epilogues read and write (vk_ff_fused_bf16 holds its out-projection to the same rules: it runs these epilogues)
+inline bool epilogue_operands_ok(const VkGemmDesc* d) {
+    // out: float4 stores (fp32), uint2 stores (16-bit; EPI_TRANS rows are S % 4 keys apart); rows ldc apart
+    if (!aligned_to(d->out, d->out_f32 ? 16 : 8)) return false;
+    if (d->epi != EPI_TRANS && (d->ldc % 4) != 0) return false;
+    // residuals: uint2 loads
+    if (d->res1 && (!aligned_to(d->res1, 8) || (d->ld_res1 % 4) != 0)) return false;
+    if (d->res2 && (!aligned_to(d->res2, 8) || (d->ld_res2 % 4) != 0)) return false;
+    // per-column / per-image vectors: float4 loads (EPI_TRANS reads its lane's one channel: a float)
+    const size_t vec = d->epi == EPI_TRANS ? 4 : 16;
+    if (!aligned_to(d->bias, vec) || (d->ln_stats && !aligned_to(d->ln_colsum, vec))) return false;
+    if ((d->rowvec || d->rowvec2) && (!aligned_to(d->rowvec, 16) || !aligned_to(d->rowvec2, 16) || (d->ldv % 4) != 0)) return false;
+    // (sum, sum of squares) pairs as float2; GroupNorm slots as floats; split-K partials as float4
+    if (!aligned_to(d->ln_stats, 8) || !aligned_to(d->rowstat_out, 8) || !aligned_to(d->gnstat_out, 4) || !aligned_to(d->splitk_ws, 16)) return false;
+    return true;
+}
+inline bool operands_ok(const VkGemmDesc* d) {
+    // loaders: 16-byte pieces (LDS-DMA dwordx4, uint4) of rows that are lda / lda2 / Cin elements apart (lda % 8, lda2 % 8, Cin % 64: validate())
+    if (!aligned_to(d->A, 16) || !aligned_to(d->Wt, 16) || !aligned_to(d->A2, 16) || !aligned_to(d->halo_prev, 16) || !aligned_to(d->halo_next, 16)) return false;
+    return epilogue_operands_ok(d);
 }
 
 // one float4 per thread: section s of the region = [bias | colsum | rowvec of images img0.. | rowvec2 of images img0..], absent ones zero
@@ -599,7 +628,7 @@ __device__ __forceinline__ void epilogue_linear_lds_body(const VkGemmDesc& p, f3
                     const uint2 r = NRES == 2 ? qb[g] : qa[g];
                     const float4 b2 = *(const float4*)(evr2 + co);
                     const float t0 = bf16_lo(r.x) + b2.x, t1 = bf16_hi(r.x) + b2.y, t2 = bf16_lo(r.y) + b2.z, t3 = bf16_hi(r.y) + b2.w;
-                    v[0] += p.beta * t0; v[1] += p.beta * t1; v[2] += p.beta * t2; v[3] += p.beta * t3;
+                    v[0] = fmaf(p.beta, t0, v[0]); v[1] = fmaf(p.beta, t1, v[1]); v[2] = fmaf(p.beta, t2, v[2]); v[3] = fmaf(p.beta, t3, v[3]);
                 }
                 if constexpr (mx_tile) {
 #pragma unroll

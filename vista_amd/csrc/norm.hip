@@ -552,6 +552,8 @@ int gn_stats(const void* x, const void* x2, int C1, float* sums, float* partial_
     hipStream_t stream = (hipStream_t)stream_;
     GnGeom g;
     if (!x || !sums || !partial_ws || !gn_geom(n_img, S, C, frames_per_group, g) || (pivot && amax_part)) return VK_EINVAL;
+    // operand contract (include/vista_hip.h): 16-byte loads of 8-channel chunks; the sums are floats
+    if (!aligned_to(x, 16) || !aligned_to(x2, 16) || !aligned_to(sums, 4) || !aligned_to(partial_ws, 4) || !aligned_to(amax_part, 4)) return VK_EINVAL;
     dim3 grid(g.nchunks, n_img);
     const size_t lds_bytes = (size_t)2 * g.R * C * sizeof(float);
     if (amax_part)
@@ -583,6 +585,7 @@ int gn_apply(const void* x, const void* x2, int C1, void* y, const float* gamma,
     hipStream_t stream = (hipStream_t)stream_;
     GnGeom g;
     if (!x || !y || !gamma || !beta || !sums || count <= 0.f || !gn_geom(n_img, S, C, frames_per_group, g)) return VK_EINVAL;
+    if (!aligned_to(x, 16) || !aligned_to(x2, 16) || !aligned_to(y, 16) || !aligned_to(gamma, 4) || !aligned_to(beta, 4) || !aligned_to(sums, 4)) return VK_EINVAL;
     const int tok_per_wg = g.tok;
     dim3 grid(g.nchunks, n_img);
     // Non-temporal hints for tensors that do not fit the 256 MiB Infinity Cache anyway (levels 0 and 1 at the BASELINE window: 295 / 147 MB): the
@@ -643,7 +646,7 @@ extern "C" int vk_groupnorm_apply_partials_bf16(const void* x, void* y, const fl
 // ABI v6: stage 2 alone, on the stage-1 slots a GEMM epilogue wrote (VkGemmDesc.gnstat_out: one slot per 64 output rows)
 extern "C" int vk_groupnorm_finalize_partials(float* partial, float* sums, int32_t n_img, int32_t nchunks, int32_t frames_per_group, void* stream_) {
     if (!partial || !sums || n_img <= 0 || nchunks <= 0 || frames_per_group <= 0 || (n_img % frames_per_group) != 0) return VK_EINVAL;
-    if ((long long)frames_per_group * nchunks > (1LL << 24)) return VK_EINVAL;
+    if ((long long)frames_per_group * nchunks > (1LL << 24) || !aligned_to(partial, 4) || !aligned_to(sums, 4)) return VK_EINVAL;
     return gn_finalize(partial, sums, n_img / frames_per_group, frames_per_group * nchunks, (hipStream_t)stream_);
 }
 
@@ -651,6 +654,9 @@ extern "C" int vk_groupnorm_silu_cat_bf16(const void* x1, const void* x2, void* 
                                           int32_t n_img, int32_t S, int32_t C1, int32_t C2, int32_t frames_per_group, float eps, int32_t silu,
                                           void* stream_) {
     if (!x1 || !x2 || !stats_ws || frames_per_group <= 0 || n_img <= 0 || C1 <= 0 || C2 <= 0 || (C1 % 8) != 0 || (C2 % 8) != 0) return VK_EINVAL;
+    // every operand of BOTH passes before the first launch (the apply pass would refuse y / gamma / beta only after the statistics pass had run)
+    if (!y || !gamma || !beta || !aligned_to(x1, 16) || !aligned_to(x2, 16) || !aligned_to(y, 16) || !aligned_to(gamma, 4) || !aligned_to(beta, 4) || !aligned_to(stats_ws, 4))
+        return VK_EINVAL;
     const int C = C1 + C2;
     float* partial = stats_ws + (size_t)(n_img / frames_per_group) * 64;
     const int fold = gn_fold_parts(n_img, S, C, frames_per_group);
@@ -685,6 +691,7 @@ extern "C" int vk_groupnorm_silu_fp8(const void* x1, const void* x2, void* y8, f
 
 extern "C" int vk_rowstats_bf16(const void* x, float* stats, int32_t rows, int32_t C, int64_t ldx, void* stream_) {
     if (!x || !stats || rows <= 0 || C <= 0 || (C % 8) != 0 || C > 1536 || ldx < C || (ldx % 8) != 0) return VK_EINVAL;
+    if (!aligned_to(x, 16) || !aligned_to(stats, 8)) return VK_EINVAL;   // 16-byte loads; (sum, sum of squares) stored as float2
     long long want = ((long long)rows + 3) / 4;
     const long long cap = 256LL * 16;
     hipLaunchKernelGGL(rowstats_kernel, dim3((int)(want < cap ? want : cap)), dim3(256), 0, (hipStream_t)stream_, (const uint16_t*)x, (float2*)stats,
@@ -696,6 +703,9 @@ extern "C" int vk_rowstats_bf16(const void* x, float* stats, int32_t rows, int32
 extern "C" int vk_groupnorm_silu_bf16(const void* x, void* y, const float* gamma, const float* beta, float* stats_ws, int32_t n_img,
                                       int32_t S, int32_t C, int32_t frames_per_group, float eps, int32_t silu, void* stream_) {
     if (!stats_ws || frames_per_group <= 0 || n_img <= 0) return VK_EINVAL;
+    // every operand of BOTH passes before the first launch (the apply pass would refuse y / gamma / beta only after the statistics pass had run)
+    if (!x || !y || !gamma || !beta || !aligned_to(x, 16) || !aligned_to(y, 16) || !aligned_to(gamma, 4) || !aligned_to(beta, 4) || !aligned_to(stats_ws, 4)) return VK_EINVAL;
+    if (GN_PIVOT && y == x) return VK_EINVAL;   // (the pivoted build's in-place refusal, likewise before the statistics pass)
     // workspace: [n_img/fpg][64] sums, then [n_img][chunks][64] partial sums
     float* partial = stats_ws + (size_t)(n_img / frames_per_group) * 64;
     const int fold = gn_fold_parts(n_img, S, C, frames_per_group);
@@ -710,6 +720,7 @@ extern "C" int vk_layernorm_bf16(const void* x, void* y, void* sum_out, const fl
     hipStream_t stream = (hipStream_t)stream_;
     if (!x || !y || !gamma || !beta || rows <= 0 || C <= 0 || (C % 8) != 0 || C > 1536) return VK_EINVAL;
     if (addvec && rows_per_vec <= 0) return VK_EINVAL;
+    if (!aligned_to(x, 16) || !aligned_to(y, 16) || !aligned_to(sum_out, 16) || !aligned_to(gamma, 4) || !aligned_to(beta, 4) || !aligned_to(addvec, 4)) return VK_EINVAL;
     const int CG = C / 8;
     const int nch = (CG + 63) / 64;
     long long want = ((long long)rows + 3) / 4;

@@ -93,6 +93,72 @@ def ceil_to(x, m):
     return (x + m - 1) // m * m
 
 
+# ---------------------------------------------------------------------------------------------- operand contract
+# What the kernels ask of every tensor they are handed (include/vista_hip.h states it beside each prototype; the C entry points refuse the same
+# with VK_EINVAL): the storage dtype, the device, contiguous rows, a base address and a row stride that suit the widest access the kernels make,
+# and an extent that covers every row and column the geometry arguments name. Checked here, before the launch, so that a wrong slice in model code
+# is a ValueError that names the operand instead of a read or a write past a tensor. Refused, never cloned: a silent copy of a 600 MB activation
+# would hide the bug (the `_aligned16` clones of the small front-door operands are another matter and stay).
+# Cost: one pass over attributes torch already holds; every test is in the one `if` of the accepting path (measured against the parent commit on the
+# eager and the graph-replay step: profiles/operand_contract.txt).
+class OperandError(ValueError):
+    """An operand outside its contract: refused before any launch."""
+
+
+def _refuse(name, t, rule):
+    if not t.is_cuda:
+        raise _lib.VistaHipError(f"{name}: tensor is on {t.device}; vista_amd kernels run on the MI355X only (no CPU fallback)")
+    raise OperandError(f"{name}: {rule} (got {tuple(t.shape)} {t.dtype} on {t.device}, strides {tuple(t.stride())}, address % 16 = {t.data_ptr() & 15})")
+
+
+def _operand(t, name, dtype, dev, align, rows, cols, ld_mult=1, exact_cols=False):
+    """t: a 2-D view with contiguous rows, of `dtype` on GPU `dev` (a device index: tensor.get_device(), -1 = not a GPU), base address a multiple of `align` bytes, row stride a multiple of `ld_mult`
+    elements and >= its columns, >= rows x cols (exact_cols: exactly cols columns). Returns the row stride."""
+    sh, st = t.shape, t.stride()
+    if (t.dtype is dtype and len(sh) == 2 and st[1] == 1 and t.get_device() == dev and dev >= 0 and (t.data_ptr() & (align - 1)) == 0 and st[0] % ld_mult == 0
+            and sh[0] >= rows and (sh[1] == cols if exact_cols else sh[1] >= cols) and (st[0] >= sh[1] or sh[0] == 1)):
+        return st[0]
+    if t.dtype is not dtype or not t.is_cuda:
+        _refuse(name, t, f"dtype must be {dtype}")
+    if t.get_device() != dev:
+        _refuse(name, t, f"must be on cuda:{dev}, the device of the call's first operand")
+    if len(sh) != 2 or st[1] != 1:
+        _refuse(name, t, "must be a 2-D view with stride(-1) == 1")
+    if t.data_ptr() & (align - 1):
+        _refuse(name, t, f"base address must be a multiple of {align} bytes")
+    if st[0] % ld_mult or (st[0] < sh[1] and sh[0] != 1):
+        _refuse(name, t, f"row stride must be a multiple of {ld_mult} elements and cover the row")
+    _refuse(name, t, f"needs at least {rows} rows and {'exactly' if exact_cols else 'at least'} {cols} columns")
+
+
+def _token_rows(t, name, dtype, dev, align, rows, cols):
+    """_operand for a token-major tensor that may be 3-D (n_img, S, ld-strided C): its rows, flattened, must be uniformly strided."""
+    if t.dim() == 3 and t.stride(0) == t.shape[1] * t.stride(1):
+        t = t.as_strided((t.shape[0] * t.shape[1], t.shape[2]), (t.stride(1), t.stride(2)), t.storage_offset())
+    return _operand(t, name, dtype, dev, align, rows, cols)
+
+
+def _affine(gamma, beta, Cc, dev):
+    """gamma / beta of a norm over Cc channels: fp32, contiguous, exactly Cc long, on the input's device."""
+    _dense(gamma, "gamma", F32, dev, 4, Cc)
+    _dense(beta, "beta", F32, dev, 4, Cc)
+
+
+def _dense(t, name, dtype, dev, align, numel):
+    """t: contiguous, of `dtype` on `dev`, base address a multiple of `align` bytes, exactly `numel` elements (what the geometry arguments state)."""
+    if t.dtype is dtype and t.get_device() == dev and dev >= 0 and (t.data_ptr() & (align - 1)) == 0 and t.numel() == numel and t.is_contiguous():
+        return
+    if t.dtype is not dtype or not t.is_cuda:
+        _refuse(name, t, f"dtype must be {dtype}")
+    if t.get_device() != dev:
+        _refuse(name, t, f"must be on cuda:{dev}, the device of the call's first operand")
+    if not t.is_contiguous():
+        _refuse(name, t, "must be contiguous")
+    if t.data_ptr() & (align - 1):
+        _refuse(name, t, f"base address must be a multiple of {align} bytes")
+    _refuse(name, t, f"must hold exactly {numel} elements, the extent the geometry arguments state")
+
+
 # ---------------------------------------------------------------------------------------------- weight packing
 class PackedWeight:
     """bf16 [ceil256(N)][K] weight (K contiguous) + f32 bias, laid out for vk_gemm_bf16. `colsum` (f32 [Np]) marks a weight with a
@@ -101,6 +167,9 @@ class PackedWeight:
     __slots__ = ("wt", "bias", "N", "K", "geglu", "colsum", "ln_eps", "ffout", "classes")
 
     def __init__(self, wt, bias, N, K, geglu=False, colsum=None, ln_eps=0.0, ffout=False, classes=1):
+        for name, t in (("wt", wt), ("bias", bias), ("colsum", colsum)):   # operand contract, once per pack: 16-byte LDS-DMA pieces / float4 loads
+            if t is not None and (t.data_ptr() & 15 or not t.is_contiguous() or t.device != wt.device):
+                _refuse(f"PackedWeight.{name}", t, "must be contiguous, 16-byte aligned and on the weight's device")
         self.wt, self.bias, self.N, self.K, self.geglu, self.colsum, self.ln_eps = wt, bias, N, K, geglu, colsum, ln_eps
         self.ffout = ffout  # laid out for vk_ff_fused_bf16's out-projection (pack_ff_out): not a vk_gemm_bf16 operand
         self.classes = classes  # 4: the class packs of a folded upsample convolution (pack_upconv2x2), one after another; only ops.upconv2x2 takes it
@@ -430,32 +499,41 @@ def _fill_ln(d, pw, ln, M):
         d.ln_stats, d.ln_parts, d.ln_colsum, d.ln_eps = _p(ln.t), ln.parts, _p(pw.colsum), pw.ln_eps
 
 
-def _fill_epilogue(d, pw, out, M, rowvec, rows_per_vec, res1, res2, alpha, beta, rowvec2=None):
+def _fill_epilogue(d, pw, out, M, rowvec, rows_per_vec, res1, res2, alpha, beta, rowvec2=None, ncols=None, out_dtype=None):
+    """The epilogue operands of a GEMM over M rows into `out` (M x ncols; ncols: pw.N unless the caller says otherwise -- GEGLU, mx8_cols), each
+    held to the operand contract: out 8-byte aligned (fp32: 16) with ldc % 4, residuals 8-byte aligned with ld % 4 and >= M x N, row vectors fp32,
+    16-byte aligned, ldv % 4, >= ceil(M / rows_per_vec) x N. out_dtype: the fp8 GEGLU's MX output (e4m3 bytes, 16-byte aligned) instead of a 16-bit / fp32 one."""
+    dev = pw.wt.get_device()
     d.Wt = _p(pw.wt)
     d.bias = _p(pw.bias)
     d.M, d.N, d.K = M, pw.N, pw.K
-    d.out = _p(out)
-    d.ldc = out.stride(0)
-    d.out_f32 = 1 if out.dtype == F32 else 0
+    if out is None:   # a plan query asked before the output exists (upconv2x2_fits): any 16-byte aligned device pointer, never written
+        f32, d.out, d.ldc = False, d.Wt, pw.N
+    else:
+        f32 = out.dtype is F32
+        d.ldc = _operand(out, "out", out_dtype or (F32 if f32 else BF16), dev, 16 if (f32 or out_dtype is not None) else 8, M, pw.N if ncols is None else ncols, 4,
+                         exact_cols=True)
+        d.out = _p(out)
+    d.out_f32 = 1 if f32 else 0
     d.alpha, d.beta = float(alpha), float(beta)
+    if rowvec is not None or rowvec2 is not None:
+        if int(rows_per_vec) <= 0:
+            raise ValueError("rowvec / rowvec2: rows_per_vec must be positive")
+        nvec = (M + int(rows_per_vec) - 1) // int(rows_per_vec)
     if rowvec is not None:
-        _need(rowvec, F32, "rowvec")
-        d.rowvec, d.ldv, d.rows_per_vec = _p(rowvec), rowvec.stride(0), int(rows_per_vec)
+        d.rowvec, d.ldv, d.rows_per_vec = _p(rowvec), _operand(rowvec, "rowvec", F32, dev, 16, nvec, pw.N, 4), int(rows_per_vec)
     if res1 is not None:
-        _need(res1, BF16, "res1")
         r, ld = _rows2d(res1, "res1")
-        d.res1, d.ld_res1 = _p(r), ld
+        d.res1, d.ld_res1 = _p(r), _operand(r, "res1", BF16, dev, 8, M, pw.N, 4)
     if res2 is not None:
-        _need(res2, BF16, "res2")
         r, ld = _rows2d(res2, "res2")
-        d.res2, d.ld_res2 = _p(r), ld
+        d.res2, d.ld_res2 = _p(r), _operand(r, "res2", BF16, dev, 8, M, pw.N, 4)
     if rowvec2 is not None:
-        _need(rowvec2, F32, "rowvec2")
         if res2 is None:
             raise ValueError("rowvec2 is added to res2 (out = alpha*(...) + beta*(res2 + rowvec2))")
         if rowvec is not None and rowvec.stride(0) != rowvec2.stride(0):
             raise ValueError("rowvec and rowvec2 share one row stride")
-        d.rowvec2, d.ldv, d.rows_per_vec = _p(rowvec2), rowvec2.stride(0), int(rows_per_vec)
+        d.rowvec2, d.ldv, d.rows_per_vec = _p(rowvec2), _operand(rowvec2, "rowvec2", F32, dev, 16, nvec, pw.N, 4), int(rows_per_vec)
 
 
 def linear(x, pw, *, out=None, out_f32=False, rowvec=None, rows_per_vec=0, res1=None, res2=None, alpha=1.0, beta=0.0, rowvec2=None,
@@ -463,16 +541,16 @@ def linear(x, pw, *, out=None, out_f32=False, rowvec=None, rows_per_vec=0, res1=
     """out = alpha*(act(X @ W^T + bias + rowvec[row // rows_per_vec]) + res1) + beta*(res2 + rowvec2[row // rows_per_vec]); act: None | "gelu".
     x: (..., K) bf16. x2: second source of a channel concat, X = [x | x2] (never materialised). ln: RowStats of x's rows when pw has
     a LayerNorm folded in (X = LayerNorm(x)). emit_stats: also return the RowStats of the (bf16) output -> (out, stats)."""
-    _need(x, BF16, "x")
     x2d, lda = _rows2d(x, "x")
     M = x2d.shape[0]
     k_in = x2d.shape[1]
+    _operand(x2d, "x", BF16, pw.wt.get_device(), 16, M, k_in, 8)
     d = VkGemmDesc()
     if x2 is not None:
-        _need(x2, BF16, "x2")
         b2d, ldb = _rows2d(x2, "x2")
         if b2d.shape[0] != M:
             raise ValueError("linear: x and x2 must have the same rows")
+        _operand(b2d, "x2", BF16, pw.wt.get_device(), 16, M, b2d.shape[1], 8)
         d.A2, d.lda2, d.k_split = _p(b2d), ldb, k_in
         k_in += b2d.shape[1]
     if k_in != pw.K:
@@ -488,7 +566,7 @@ def linear(x, pw, *, out=None, out_f32=False, rowvec=None, rows_per_vec=0, res1=
     d.A, d.lda = _p(x2d), lda
     d.amode = AMODE_DENSE
     d.epi = EPI_GEGLU if pw.geglu else EPI_LINEAR
-    _fill_epilogue(d, pw, out, M, rowvec, rows_per_vec, res1, res2, alpha, beta, rowvec2)
+    _fill_epilogue(d, pw, out, M, rowvec, rows_per_vec, res1, res2, alpha, beta, rowvec2, ncols=pw.N // 2 if pw.geglu else pw.N - mx8_cols)
     _fill_ln(d, pw, ln, M)
     mx = None
     if mx8_cols:
@@ -513,13 +591,16 @@ def linear(x, pw, *, out=None, out_f32=False, rowvec=None, rows_per_vec=0, res1=
 
 def linear_vt(x, pw, S, out=None, ln=None):
     """V^T projection for spatial attention: x (n_img*S, K) -> out (n_img, N, S) bf16 = (x @ W^T + bias)^T per image (EPI_TRANS)."""
-    _need(x, BF16, "x")
     x2, lda = _rows2d(x, "x")
     M = x2.shape[0]
+    _operand(x2, "x", BF16, pw.wt.get_device(), 16, M, pw.K, 8, exact_cols=True)
+    if S <= 0 or M % S:
+        raise ValueError(f"linear_vt: x has {M} rows, not a multiple of S = {S}")
     if out is None:
         out = torch.empty((M // S, pw.N, S), dtype=BF16, device=x.device)
     elif out.dtype != BF16 or not out.is_contiguous() or out.shape != (M // S, pw.N, S):
         raise ValueError("linear_vt: out must be contiguous bf16 (n_img, N, S)")
+    _dense(out, "out", BF16, pw.wt.get_device(), 8, M * pw.N)
     d = VkGemmDesc()
     d.A, d.lda = _p(x2), lda
     d.amode, d.epi = AMODE_DENSE, EPI_TRANS
@@ -533,9 +614,9 @@ def linear_vt(x, pw, S, out=None, ln=None):
 
 def rowstats(x):
     """RowStats (one slab) of x (..., C) bf16 by a read-only pass: for tensors whose producer is not a GEMM epilogue on this rank."""
-    _need(x, BF16, "x")
     x2, ldx = _rows2d(x, "x")
     M, Cc = x2.shape
+    _operand(x2, "x", BF16, x.get_device(), 16, M, Cc, 8)
     st = torch.empty((1, M, 2), dtype=F32, device=x.device)
     check(_lib.load().vk_rowstats_bf16(_p(x2), _p(st), M, Cc, ldx, _stream()), "vk_rowstats_bf16")
     return RowStats(st, 1, M)
@@ -556,9 +637,9 @@ def ff_fused(x, pw_in, pw_out, *, out=None, rowvec=None, rows_per_vec=0, res1=No
              emit_stats=False):
     """linear(linear(x, pw_in, ln=ln), pw_out', ...epilogue) in ONE kernel (vk_ff_fused_bf16): pw_in = pack_geglu(...), pw_out' =
     pack_ff_out(...). The hidden activation never leaves the CU. Returns out, or (out, RowStats) with emit_stats."""
-    _need(x, BF16, "x")
     x2d, lda = _rows2d(x, "x")
     M = x2d.shape[0]
+    _operand(x2d, "x", BF16, pw_in.wt.get_device(), 16, M, x2d.shape[1], 8)
     if not ff_fused_ok(pw_in, pw_out) or not pw_out.ffout or x2d.shape[1] != pw_in.K:
         raise ValueError("ff_fused: needs a packed GEGLU weight [2H][320] and a pack_ff_out weight [320][H], H % 64 == 0, 128 <= H <= 1280")
     if out is None:
@@ -591,10 +672,8 @@ def conv3x3(x, pw, n_img, H, W, *, stride=1, ups=1, out=None, out_f32=False, row
             beta=0.0, asym_pad=False, gn=None):
     """3x3 conv, pad 1, over token-major x (n_img, H*W, Cin); `ups`=2 applies a nearest x2 upsample to the source
     on the fly (Upsample.forward, openaimodel.py:100-102); stride 2 = Downsample (openaimodel.py:136)."""
-    _need(x, BF16, "x")
-    if not x.is_contiguous():
-        raise ValueError("conv3x3: x must be contiguous")
     cin = x.shape[-1]
+    _dense(x, "x", BF16, pw.wt.get_device(), 16, n_img * H * W * cin)
     if pw.K != 9 * cin:
         raise ValueError(f"conv3x3: weight K {pw.K} != 9*{cin}")
     He, We = H * ups, W * ups
@@ -636,10 +715,7 @@ def _upconv_desc(x, pw, n_img, H, W, rowvec, out):
 def upconv2x2_fits(x, pw, n_img, H, W, rowvec=None, out=None):
     """Does the library take the folded form of this upsample convolution (host arithmetic, no launch)? It does where the nine-tap form would run on
     the pipelined 256x320 kernel in one launch: Cout % 320 == 0 and enough rows to fill the chip; else the caller runs ops.conv3x3(..., ups=2)."""
-    if out is None:
-        out = x   # (any 16-byte aligned device pointer: the answer depends on alignment and extents only)
-    d, _ = _upconv_desc(x, pw, n_img, H, W, rowvec, out)
-    d.ldc = pw.N
+    d, _ = _upconv_desc(x, pw, n_img, H, W, rowvec, out)   # (out None: the answer depends on alignment and extents only)
     return _lib.load().vk_gemm_tile_choice(C.byref(d)) > 0
 
 
@@ -647,10 +723,8 @@ def upconv2x2(x, pw, n_img, H, W, rowvec=None, out=None):
     """Upsample.forward (openaimodel.py:100-102: nearest x2, then conv3x3 pad 1) on a pack_upconv2x2 pack: four 2x2 class convolutions of the source,
     K = 4 Cin instead of 9 Cin, scattered to the output pixels of their parity. x (n_img, H*W, Cin) -> ((n_img, 4*H*W, Cout), 2H, 2W). Raises where the
     library declines the shape (upconv2x2_fits): there is no quiet change of algorithm here."""
-    _need(x, BF16, "x")
-    if not x.is_contiguous():
-        raise ValueError("upconv2x2: x must be contiguous")
     cin = x.shape[-1]
+    _dense(x, "x", BF16, pw.wt.get_device(), 16, n_img * H * W * cin)
     if pw.classes != 4 or pw.K != 4 * cin:
         raise ValueError(f"upconv2x2: needs a pack_upconv2x2 weight with K = 4*{cin}")
     M = n_img * 4 * H * W
@@ -665,10 +739,10 @@ def conv_t3(x, pw, T, S, *, out=None, out_f32=False, rowvec=None, res1=None, res
             halo_next=None, gn=None):
     """3x1x1 temporal conv, pad (1,0,0) (video_model.py:38-52) over x ((b t), S, C). halo_prev / halo_next: (clips, S, C) frames
     adjacent to the local frame range (frame-sharded multi-GPU); None = zero padding."""
-    _need(x, BF16, "x")
-    if not x.is_contiguous():
-        raise ValueError("conv_t3: x must be contiguous")
     cin = x.shape[-1]
+    if x.dim() != 3 or T <= 0 or x.shape[0] % T or x.shape[1] != S:
+        raise ValueError(f"conv_t3: x must be ((b t), S, C) with (b t) a multiple of T = {T} and S = {S}, got {tuple(x.shape)}")
+    _dense(x, "x", BF16, pw.wt.get_device(), 16, x.shape[0] * S * cin)
     if pw.K != 3 * cin:
         raise ValueError("conv_t3: weight K mismatch")
     M = x.shape[0] * x.shape[1]
@@ -680,9 +754,9 @@ def conv_t3(x, pw, T, S, *, out=None, out_f32=False, rowvec=None, res1=None, res
     d.Cin, d.T, d.S = cin, T, S
     for name, h in (("halo_prev", halo_prev), ("halo_next", halo_next)):
         if h is not None:
-            _need(h, BF16, name)
-            if not h.is_contiguous() or h.shape != (x.shape[0] // T, S, cin):
+            if h.shape != (x.shape[0] // T, S, cin):
                 raise ValueError(f"{name}: expected contiguous (clips, S, C) = {(x.shape[0] // T, S, cin)}, got {tuple(h.shape)}")
+            _dense(h, name, BF16, pw.wt.get_device(), 16, h.numel())
             setattr(d, name, _p(h))
     _fill_epilogue(d, pw, out, M, rowvec, S, res1, res2, alpha, beta)
     _ask_gn(d, gn, S, x.device)
@@ -702,10 +776,10 @@ def pack_conv3d(weight, bias=None, device="cuda", cin_pad=None):
 
 def conv3d(x, pw, T, H, W, *, out=None, out_f32=False, res1=None, res2=None, alpha=1.0, beta=0.0):
     """3x3x3 conv, pad 1, over x ((b t), H*W, Cin) with clips of T frames (AE3DConv.time_mix_conv and the decoder's time_stack)."""
-    _need(x, BF16, "x")
-    if not x.is_contiguous():
-        raise ValueError("conv3d: x must be contiguous")
     cin = x.shape[-1]
+    if T <= 0 or x.shape[0] % T:
+        raise ValueError(f"conv3d: x has {x.shape[0]} frames, not a multiple of T = {T}")
+    _dense(x, "x", BF16, pw.wt.get_device(), 16, x.shape[0] * H * W * cin)
     if pw.K != 27 * cin:
         raise ValueError(f"conv3d: weight K {pw.K} != 27*{cin}")
     M = x.shape[0] * H * W
@@ -894,7 +968,7 @@ def linear_fp8(xq, a_scale, pw, *, out=None, out_f32=False, rowvec=None, rows_pe
     d.A, d.lda = _p(xq), xq.stride(0)
     d.amode = AMODE_DENSE
     d.epi = EPI_GEGLU if pw.geglu else EPI_LINEAR
-    _fill_epilogue(d, pw, out, M, rowvec, rows_per_vec, res1, res2, alpha, beta, rowvec2)
+    _fill_epilogue(d, pw, out, M, rowvec, rows_per_vec, res1, res2, alpha, beta, rowvec2, ncols=nout, out_dtype=torch.uint8 if out.dtype is torch.uint8 else None)
     d.K = pw.Kp
     d.tile_cfg = TILE_CFG & 7
     lib = _lib.load()
@@ -931,8 +1005,18 @@ def attn_spatial(q, k, vt, n_img, heads, S, scale=None, v_rows=False, q_log2=Fal
     2-D strided view (n_img*S, heads*64) like q and k -- the v column block of ONE fused q|k|v GEMM. Returns (n_img*S, heads*64).
     q_log2 (with v_rows): q already carries softmax_scale * log2(e) (folded into the query weights at pack time), so q.k is the base-2
     exponent itself and the kernel's zero-base path needs no scale / base fma (vk_attn_spatial_qkv_log2_bf16); `scale` is not used."""
-    _need(q, BF16, "q"); _need(k, BF16, "k"); _need(vt, BF16, "v" if v_rows else "vt")
-    o = torch.empty((n_img * S, heads * 64), dtype=BF16, device=q.device)
+    M, c = n_img * S, heads * 64
+    _operand(q, "q", BF16, q.get_device(), 16, M, c, 8, exact_cols=True)
+    _operand(k, "k", BF16, q.get_device(), 16, M, c, 8, exact_cols=True)
+    if v_rows:
+        _operand(vt, "v", BF16, q.get_device(), 16, M, c, 8, exact_cols=True)
+    else:
+        if vt.shape != (n_img, c, S):
+            _refuse("vt", vt, f"must be (n_img, heads*64, S) = {(n_img, c, S)}")
+        _dense(vt, "vt", BF16, q.get_device(), 16, M * c)
+    if S % 8:
+        raise ValueError(f"attn_spatial: S = {S} must be a multiple of 8")
+    o = torch.empty((M, c), dtype=BF16, device=q.device)
     lib = _lib.load()
     ev = None
     if PROFILE_ATTN is not None:
@@ -940,8 +1024,6 @@ def attn_spatial(q, k, vt, n_img, heads, S, scale=None, v_rows=False, q_log2=Fal
         ev[0].record()
     sc = float(scale if scale is not None else 1.0 / math.sqrt(64))
     if v_rows:
-        if vt.dim() != 2 or vt.stride(1) != 1 or vt.shape != (n_img * S, heads * 64):
-            raise ValueError("attn_spatial: v must be a (n_img*S, heads*64) view with contiguous rows")
         if q_log2:
             check(lib.vk_attn_spatial_qkv_log2_bf16(_p(q), _p(k), _p(vt), _p(o), n_img, heads, S, q.stride(0), k.stride(0), vt.stride(0), o.stride(0),
                                                     _stream()), "vk_attn_spatial_qkv_log2_bf16")
@@ -994,10 +1076,10 @@ def attn_spatial_fp8qk(q8, k8, qs, ks, v, n_img, heads, S, scale=None, mx_out=Fa
 def attn_small(qkv, n_img, heads, S, D, scale=None):
     """qkv: (n_img*S, 3*heads*D) bf16 row-major [q | k | v]; softmax(q k^T * scale) v per (image, head), D in {64, 80, 128}
     (the OpenCLIP image tower's nn.MultiheadAttention). Returns (n_img*S, heads*D)."""
-    _need(qkv, BF16, "qkv")
     c = heads * D
-    if qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape != (n_img * S, 3 * c):
-        raise ValueError(f"attn_small: qkv must be (n_img*S, 3*heads*D) = {(n_img * S, 3 * c)} with contiguous rows, got {tuple(qkv.shape)}")
+    _operand(qkv, "qkv", BF16, qkv.get_device(), 16, n_img * S, 3 * c, 8, exact_cols=True)
+    if qkv.shape[0] != n_img * S:
+        _refuse("qkv", qkv, f"must be (n_img*S, 3*heads*D) = {(n_img * S, 3 * c)}")
     o = torch.empty((n_img * S, c), dtype=BF16, device=qkv.device)
     check(_lib.load().vk_attn_small_bf16(_p(qkv), _p(o), n_img, heads, S, D, qkv.stride(0), c, 2 * c, o.stride(0),
                                          float(scale if scale is not None else 1.0 / math.sqrt(D)), _stream()), "vk_attn_small_bf16")
@@ -1041,8 +1123,10 @@ def clip_preprocess_patches(img, out_hw=224, patch=14, kpad=None, antialias=True
 
 def attn_temporal(qkv, B, T, S, heads, scale=None):
     """qkv: ((b t) s, 3*heads*64) bf16 row-major [q | k | v]. Returns ((b t) s, heads*64)."""
-    _need(qkv, BF16, "qkv")
     c = heads * 64
+    _operand(qkv, "qkv", BF16, qkv.get_device(), 16, B * T * S, 3 * c, 8, exact_cols=True)
+    if qkv.shape[0] != B * T * S:
+        _refuse("qkv", qkv, f"must be ((b t) s, 3*heads*64) = {(B * T * S, 3 * c)}")
     o = torch.empty((B * T * S, c), dtype=BF16, device=qkv.device)
     lib = _lib.load()
     check(lib.vk_attn_temporal_bf16(_p(qkv), _p(o), B, T, S, heads, qkv.stride(0), c, 2 * c, o.stride(0),
@@ -1053,12 +1137,14 @@ def attn_temporal(qkv, B, T, S, heads, scale=None):
 # ---------------------------------------------------------------------------------------------- norms
 def softmax_rows(x, out=None):
     """x (rows, cols) fp32 (row stride may exceed cols) -> bf16 softmax over the last dim (VAE decoder AttnBlock)."""
-    _need(x, F32, "x")
+    if x.dim() != 2:
+        _refuse("x", x, "must be 2-D")
     rows, cols = x.shape
-    if x.stride(1) != 1:
-        raise ValueError("softmax_rows: rows must be contiguous")
+    _operand(x, "x", F32, x.get_device(), 16, rows, cols, 4)
     if out is None:
         out = torch.empty((rows, cols), dtype=BF16, device=x.device)
+    else:
+        _operand(out, "out", BF16, x.get_device(), 8, rows, cols, 4, exact_cols=True)
     check(_lib.load().vk_softmax_rows_f32_bf16(_p(x), _p(out), rows, cols, x.stride(0), out.stride(0), _stream()), "vk_softmax_rows_f32_bf16")
     return out
 
@@ -1075,12 +1161,15 @@ def _gn_partials_ok(gn, n_img, S, Cc):
 def groupnorm(x, gamma, beta, eps, silu, frames_per_group=1, out=None, gn=None):
     """x (n_img, S, C) bf16 contiguous. gn: the GnPartials the producer of x filled (conv3x3 / conv_t3 (..., gn=...)): fold + apply, no
     statistics pass over x."""
-    _need(x, BF16, "x")
-    if not x.is_contiguous():
-        raise ValueError("groupnorm: x must be contiguous")
+    if x.dim() != 3:
+        _refuse("x", x, "must be (n_img, S, C)")
     n_img, S, Cc = x.shape
+    _dense(x, "x", BF16, x.get_device(), 16, n_img * S * Cc)
+    _affine(gamma, beta, Cc, x.get_device())
     if out is None:
         out = torch.empty_like(x)
+    else:
+        _dense(out, "out", BF16, x.get_device(), 16, n_img * S * Cc)
     if _gn_partials_ok(gn, n_img, S, Cc):
         lib = _lib.load()
         count = float(Cc // 32) * float(S) * float(frames_per_group)
@@ -1105,11 +1194,13 @@ def groupnorm(x, gamma, beta, eps, silu, frames_per_group=1, out=None, gn=None):
 def groupnorm_cat(a, b, gamma, beta, eps, silu, frames_per_group=1):
     """GroupNorm(32)[+SiLU] of the channel concat [a | b] ((n_img, S, C1) and (n_img, S, C2) bf16) -> (n_img, S, C1+C2), without
     materialising the concat (the skip `torch.cat` of the UNet's output blocks, video_model.py:493)."""
-    _need(a, BF16, "a"); _need(b, BF16, "b")
-    if not (a.is_contiguous() and b.is_contiguous()) or a.shape[:2] != b.shape[:2]:
+    if a.dim() != 3 or b.dim() != 3 or a.shape[:2] != b.shape[:2]:
         raise ValueError("groupnorm_cat: contiguous (n_img, S, C) inputs with equal n_img, S required")
     n_img, S, c1 = a.shape
     c2 = b.shape[2]
+    _dense(a, "a", BF16, a.get_device(), 16, n_img * S * c1)
+    _dense(b, "b", BF16, a.get_device(), 16, n_img * S * c2)
+    _affine(gamma, beta, c1 + c2, a.get_device())
     out = torch.empty((n_img, S, c1 + c2), dtype=BF16, device=a.device)
     ws = torch.empty(((n_img // frames_per_group) + n_img * ((S + 31) // 32)) * 64, dtype=F32, device=a.device)
     check(_lib.load().vk_groupnorm_silu_cat_bf16(_p(a), _p(b), _p(out), _p(gamma), _p(beta), _p(ws), n_img, S, c1, c2, frames_per_group,
@@ -1121,8 +1212,11 @@ def groupnorm_sharded(x, gamma, beta, eps, silu, frames_per_group, allreduce, gl
     """GroupNorm whose statistics also span other ranks' shards of the same images (pixel-sharded temporal ResBlock):
     local fixed-order sums -> `allreduce(sums)` (in place, SUM over ranks) -> apply with the GLOBAL element count.
     gn: the producer's GnPartials of x (as groupnorm)."""
-    _need(x, BF16, "x")
+    if x.dim() != 3:
+        _refuse("x", x, "must be (n_img, S, C)")
     n_img, S, Cc = x.shape
+    _dense(x, "x", BF16, x.get_device(), 16, n_img * S * Cc)
+    _affine(gamma, beta, Cc, x.get_device())
     out = torch.empty_like(x)
     ng = n_img // frames_per_group
     sums = torch.empty(ng * 64, dtype=F32, device=x.device)
@@ -1141,11 +1235,14 @@ def groupnorm_sharded(x, gamma, beta, eps, silu, frames_per_group, allreduce, gl
 
 def layernorm(x, gamma, beta, eps=1e-5, addvec=None, rows_per_vec=0, want_sum=False):
     """x (..., C) bf16 contiguous -> LN(x + addvec[row // rows_per_vec]); optionally also returns the sum."""
-    _need(x, BF16, "x")
-    if not x.is_contiguous():
-        raise ValueError("layernorm: x must be contiguous")
     Cc = x.shape[-1]
     rows = x.numel() // Cc
+    _dense(x, "x", BF16, x.get_device(), 16, rows * Cc)
+    _affine(gamma, beta, Cc, x.get_device())
+    if addvec is not None:
+        if int(rows_per_vec) <= 0:
+            raise ValueError("layernorm: addvec needs rows_per_vec > 0")
+        _operand(addvec, "addvec", F32, x.get_device(), 4, (rows + int(rows_per_vec) - 1) // int(rows_per_vec), Cc)
     y = torch.empty_like(x)
     s = torch.empty_like(x) if (want_sum and addvec is not None) else None
     lib = _lib.load()
@@ -1156,35 +1253,36 @@ def layernorm(x, gamma, beta, eps=1e-5, addvec=None, rows_per_vec=0, want_sum=Fa
 
 # ---------------------------------------------------------------------------------------------- elementwise
 def concat_channels(a, b):
-    _need(a, BF16, "a"); _need(b, BF16, "b")
-    if not (a.is_contiguous() and b.is_contiguous()):
-        raise ValueError("concat_channels: contiguous inputs required")
     c1, c2 = a.shape[-1], b.shape[-1]
     rows = a.numel() // c1
+    if a.shape[:-1] != b.shape[:-1]:
+        raise ValueError("concat_channels: a and b must agree in every dim but the last")
+    _dense(a, "a", BF16, a.get_device(), 16, rows * c1)
+    _dense(b, "b", BF16, a.get_device(), 16, rows * c2)
     out = torch.empty(a.shape[:-1] + (c1 + c2,), dtype=BF16, device=a.device)
     check(_lib.load().vk_concat_channels_bf16(_p(a), _p(b), _p(out), rows, c1, c2, _stream()), "vk_concat_channels_bf16")
     return out
 
 
 def nchw_to_tokens(x, cpad):
-    _need(x, F32, "x")
     n, c, h, w = x.shape
     x = x.contiguous()
+    _dense(x, "x", F32, x.get_device(), 4, n * c * h * w)
     out = torch.empty((n, h * w, cpad), dtype=BF16, device=x.device)
     check(_lib.load().vk_nchw_to_tokens_bf16(_p(x), _p(out), n, c, h * w, cpad, _stream()), "vk_nchw_to_tokens_bf16")
     return out
 
 
 def tokens_to_nchw(x, n_img, Cc, H, W):
-    _need(x, F32, "x")
+    _token_rows(x, "x", F32, x.get_device(), 4, n_img * H * W, Cc)
     out = torch.empty((n_img, Cc, H, W), dtype=F32, device=x.device)
     check(_lib.load().vk_tokens_to_nchw_f32(_p(x), _p(out), n_img, Cc, H * W, x.stride(-2), _stream()), "vk_tokens_to_nchw_f32")
     return out
 
 
 def timestep_embedding(t, dim, max_period=10000.0, out_f32=False):
-    _need(t, F32, "t")
     t = t.contiguous()
+    _dense(t, "t", F32, t.get_device(), 4, t.shape[0])
     out = torch.empty((t.shape[0], dim), dtype=F32 if out_f32 else BF16, device=t.device)
     lib = _lib.load()
     fn = lib.vk_timestep_embedding_f32 if out_f32 else lib.vk_timestep_embedding_bf16
@@ -1195,6 +1293,11 @@ def timestep_embedding(t, dim, max_period=10000.0, out_f32=False):
 def emb_combine(a, b, c, mask):
     """emb = a*mask + b*(1-mask) + c ; returns (emb f32, silu(emb) bf16)."""
     n, dim = b.shape
+    for name, t in (("a", a), ("b", b), ("c", c)):
+        if t is not None:
+            _dense(t, name, F32, b.get_device(), 4, n * dim)
+    if mask is not None:
+        _dense(mask, "mask", F32, b.get_device(), 4, n)
     emb = torch.empty((n, dim), dtype=F32, device=b.device)
     se = torch.empty((n, dim), dtype=BF16, device=b.device)
     check(_lib.load().vk_emb_combine(_p(a), _p(b), _p(c), _p(mask), _p(emb), _p(se), n, dim, _stream()), "vk_emb_combine")
@@ -1219,7 +1322,14 @@ def cast_to_bf16(x):
 
 # ---- sampler-side ----
 def sampler_prepare(x, cond_frame, mask, concat_uc, concat_c, cpad, c_in, replace):
-    T, _, H, W = x.shape
+    T, ch, H, W = x.shape
+    if ch != 4:
+        _refuse("x", x, "must be (T, 4, H, W)")
+    for name, t in (("x", x), ("cond_frame", cond_frame), ("concat_uc", concat_uc), ("concat_c", concat_c)):
+        if t is not None:
+            _dense(t, name, F32, x.get_device(), 4, T * 4 * H * W)
+    if mask is not None:
+        _dense(mask, "mask", F32, x.get_device(), 4, T)
     net_in = torch.empty((2 * T, H * W, cpad), dtype=BF16, device=x.device)
     check(_lib.load().vk_sampler_prepare(_p(x), _p(cond_frame), _p(mask), _p(concat_uc), _p(concat_c), _p(net_in), T, H * W, cpad,
                                          float(c_in), 1 if replace else 0, _stream()), "vk_sampler_prepare")
@@ -1227,7 +1337,12 @@ def sampler_prepare(x, cond_frame, mask, concat_uc, concat_c, cpad, c_in, replac
 
 
 def sampler_update(x, net_out, scale, c_out, c_skip, sigma, sigma_next):
-    T, _, H, W = x.shape
+    T, ch, H, W = x.shape
+    if ch != 4:
+        _refuse("x", x, "must be (T, 4, H, W)")
+    _dense(x, "x", F32, x.get_device(), 4, T * 4 * H * W)
+    _token_rows(net_out, "net_out", F32, x.get_device(), 4, 2 * T * H * W, 4)
+    _dense(scale, "scale", F32, x.get_device(), 4, T)
     check(_lib.load().vk_sampler_update(_p(x), _p(net_out), _p(scale), T, H * W, net_out.stride(-2), float(c_out), float(c_skip),
                                         float(sigma), float(sigma_next), _stream()), "vk_sampler_update")
     return x
