@@ -610,6 +610,60 @@ typedef struct VkStrokePlan {
 int vk_stroke_overlay_u8(const void* in, void* out, const int32_t* set_of_frame, const VkStrokePlan* plan /* HOST memory */, int32_t n,
                          int32_t H, int32_t W, void* stream);
 
+/* ------------------------------------------------------------------ denoising-loss front door (csrc/loss.hip)
+ * Added under ABI v9 without a version step, as the reward, evaluation and planning entry points were: purely additive (no existing signature,
+ * struct or meaning changes), so vk_abi_version() stays 9. fp32 in and out, storage-type independent: the same code is linked into both libraries.
+ * Forward only: these are the pieces of the reference's StandardDiffusionLoss (vwm/modules/diffusionmodules/loss.py); no gradient is built.
+ *
+ * vk_loss_noise_input: out = x + (noise + level * offset[n][c]) * ((1 - mask[n]) * sigma[n]) in one pass.
+ *   x, noise, out [n][C][hw] fp32, dense; sigma [n] fp32; mask [n] fp32 or NULL (then the factor is sigma[n]); offset [n][C] fp32 or NULL (then
+ *   the noise is taken as it is and `level` is not read).
+ *   Evaluated operation by operation as the reference does -- multiply (level * offset), add, subtract and multiply ((1 - mask) * sigma),
+ *   multiply, add -- each rounded once in fp32, nothing contracted into an FMA: the result is bit for bit torch's fp32 expression on the CPU.
+ *   16 bytes per lane where hw % 4 == 0 and x, noise and out are 16-byte aligned, one element per lane otherwise (the bits are the same).
+ *   VK_EINVAL: a NULL x / noise / sigma / out, n / C / hw <= 0, n * C > 2^31 - 1, a pointer not 4-byte aligned. */
+int vk_loss_noise_input(const float* x, const float* noise, const float* sigma, const float* mask, const float* offset, float level, float* out,
+                        int32_t n, int32_t C, int32_t hw, void* stream);
+/* vk_fourier_highpass: the reference's fourier_filter (vwm/modules/diffusionmodules/util.py) of `planes` H x W fp32 planes: the 2-D DFT, every
+ * frequency multiplied by 1 where its byte of `keep` is set and by `scale` where it is not, the inverse DFT, the real part.
+ *   keep  [H][W] bytes on the GPU, indexed by the UNSHIFTED frequency (kh, kw) (the caller evaluates the reference's disc in double precision and
+ *         undoes its fftshift: ties on the disc's edge, and the unsymmetric mask of an odd H or W, are then the reference's own).
+ *   input d = a (b == NULL), a - b (cond_mask == NULL), or (a * (1 - m) + b * m) - b with m = cond_mask[plane / planes_per_image]: formed on load,
+ *         fp32, one rounding per operation, nothing contracted. The filter is linear, so HF(predict) - HF(target) is HF of this difference.
+ *   y     [planes][H][W] fp32; must not alias a or b.
+ *   One workgroup per plane, the plane resident in LDS: two complex fp32 buffers of H * W and the fp64 twiddles (cos, sin)(2 pi j / W), j < W, and
+ *   (2 pi j / H), j < H, computed in the kernel. Four dense passes (rows, columns, inverse columns, inverse rows); every output is a sum accumulated
+ *   in fp64 in index order and rounded to fp32 once. No atomics: bitwise repeatable, and a plane's result does not depend on `planes`.
+ *   The plane it can hold: 16 * H * W + 16 * (H + W) <= VK_HIGHPASS_LDS_BYTES (160 KiB, the CU's LDS); 72 x 128, the BASELINE latent, takes 150656.
+ *   Any H, W >= 1 within that rule, odd ones included. vk_fourier_highpass_lds_bytes answers the bytes a plane takes, or VK_EINVAL.
+ *   VK_EINVAL, before any HIP call: a NULL a / keep / y, cond_mask without b, y == a or y == b, planes / planes_per_image / H / W <= 0, a float pointer
+ *   not 4-byte aligned, a plane beyond the rule above. */
+#define VK_HIGHPASS_LDS_BYTES (160 * 1024)
+int vk_fourier_highpass_lds_bytes(int32_t H, int32_t W);
+int vk_fourier_highpass(const float* a, const float* b, const float* cond_mask, const void* keep, float scale, float* y, int32_t planes,
+                        int32_t planes_per_image, int32_t H, int32_t W, void* stream);
+/* vk_loss_stats: the sums the loss of B clips of T frames is assembled from. out (the denoiser's output), target [B * T][C][hw] fp32, dense;
+ * cond_mask [B * T] fp32 or NULL; hf [B * T][C][hw] fp32 (vk_fourier_highpass's output) or NULL; l1 = 0 (squares) or 1 (absolute values).
+ *   predict = out * (1 - m) + target * m per frame (out where cond_mask is NULL), fp32, one rounding per operation, nothing contracted.
+ *   dd      = (target_t - target_{t-1}) - (predict_t - predict_{t-1}),  a = dd^2 (l2) or |dd| (l1), for t >= 1.
+ *   Launch 1, per (clip b, channel c): the sum over (t >= 1, h, w) of a^2 (l2) or of a (l1), in fp64, by VK_LOSS_STATS_BLOCKS workgroups whose
+ *   element assignment is a function of T and hw alone -> partial_ws [B][C][VK_LOSS_STATS_BLOCKS] doubles, the caller's.
+ *   Launch 2, one workgroup per frame: the clip's partials added in block order; norm = sqrt of that sum (l2) or the sum (l1), rounded to fp32
+ *   once; aux_w = 1 at t == 0, else 1 + a / max(norm, 1e-12) in fp32 (F.normalize's clamp: a norm of 0 gives aux_w = 1). Then, in fp64,
+ *     sums[f] = (S0, S1, S2) = (sum e, sum e * aux_w, sum |hf|^p),  e = (predict - target)^2 or |predict - target|, p = 2 or 1; S2 = 0 without hf.
+ *   Thread i adds the frame's groups i, i + 256, ... (a group = 4 neighbouring elements where hw % 4 == 0, else 1) and the block adds the threads
+ *   in a fixed tree: no atomics, bitwise repeatable, and a frame's sums do not depend on B or on the frames of other clips. T == 1 (no frame
+ *   differences; also how a caller asks for S0 alone): S1 == S0, launch 1 is skipped, partial_ws may be NULL and B is not limited to 65535.
+ *   A frame with m == 1 gives (0, 0, S2) exactly, and S2 == 0 exactly when hf came from vk_fourier_highpass with the same cond_mask.
+ *   The loss weight w(sigma) is not applied here: the caller weighs the sums in float64.
+ *   16-byte loads where hw % 4 == 0 and out, target and hf are 16-byte aligned; the order of every sum is a function of hw alone either way.
+ *   VK_EINVAL: a NULL out / target / sums, B / T / C / hw <= 0, C > VK_LOSS_MAX_CHANNELS, with T > 1 a NULL partial_ws or B > 65535, B * T or C * hw > 2^31 - 1, l1
+ *   not 0 or 1, a float pointer not 4-byte aligned, sums or partial_ws not 8-byte aligned. */
+#define VK_LOSS_STATS_BLOCKS 16
+#define VK_LOSS_MAX_CHANNELS 64
+int vk_loss_stats(const float* out, const float* target, const float* cond_mask, const float* hf, double* sums, double* partial_ws, int32_t B,
+                  int32_t T, int32_t C, int32_t hw, int32_t l1, void* stream);
+
 /* library info */
 int vk_abi_version(void);
 /* ABI v7: the 16-bit storage type this library was built for: 0 = bf16 (libvista_hip.so, the default and the BASELINE config's dtype), 1 = IEEE fp16

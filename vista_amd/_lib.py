@@ -150,6 +150,10 @@ SIGNATURES = {
     "vk_frame_fidelity_u8": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _vp],
     "vk_copy_row_boxes": [_vp, _vp, C.POINTER(VkRowBoxes), _i64, _i64, _i32, _vp],
     "vk_stroke_overlay_u8": [_vp, _vp, _vp, C.POINTER(VkStrokePlan), _i32, _i32, _i32, _vp],
+    "vk_loss_noise_input": [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp],
+    "vk_fourier_highpass_lds_bytes": [_i32, _i32],
+    "vk_fourier_highpass": [_vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _vp],
+    "vk_loss_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "vk_abi_version": [],
     "vk_act_dtype": [],
 }

@@ -134,6 +134,47 @@ def timestep_embedding(timesteps, dim, max_period=10000, repeat_only=False):
     return ops.timestep_embedding(timesteps.float(), dim, float(max_period))
 
 
+_KEEP_MASKS = {}
+
+
+def fourier_keep_mask(H, W, d_s=0.25):
+    """(H, W) uint8 on the host, indexed by the UNSHIFTED frequency: 0 where the reference's fourier_filter multiplies by `scale` (the centred
+    disc (2 h / H - 1)^2 + (2 w / W - 1)^2 <= 2 d_s of the fftshift-ed spectrum), 1 where it keeps the frequency. The test is the reference's own
+    expression in Python floats (double precision), position by position, so a tie on the disc's edge (the four frequencies (+-2, +-2) at 8 x 8)
+    falls where the reference puts it; for an odd H or W the shifted disc is not symmetric about frequency 0 and is left so. Cached per (H, W, d_s)."""
+    key = (int(H), int(W), float(d_s))
+    keep = _KEEP_MASKS.get(key)
+    if keep is None:
+        shifted = torch.ones((H, W), dtype=torch.uint8)
+        for h in range(H):
+            for w in range(W):
+                if (2 * h / H - 1) ** 2 + (2 * w / W - 1) ** 2 <= 2 * d_s:
+                    shifted[h, w] = 0
+        # position p of the shifted spectrum holds frequency index (p - N // 2) mod N: undo the shift
+        keep = _KEEP_MASKS[key] = torch.roll(shifted, shifts=(-(H // 2), -(W // 2)), dims=(0, 1)).contiguous()
+    return keep
+
+
+_KEEP_ON_DEVICE = {}
+
+
+def fourier_keep_mask_on(device, H, W, d_s=0.25):
+    """fourier_keep_mask uploaded as bytes, once per (device, H, W, d_s)."""
+    key = (str(device), int(H), int(W), float(d_s))
+    keep = _KEEP_ON_DEVICE.get(key)
+    if keep is None:
+        keep = _KEEP_ON_DEVICE[key] = fourier_keep_mask(H, W, d_s).to(device)
+    return keep
+
+
+def fourier_filter(x, scale, d_s=0.25):
+    """util.py:20-43 of the reference on the device: x (B, C, H, W) -> every plane's 2-D DFT, the centred disc of low frequencies multiplied by
+    `scale`, the inverse DFT, the real part, in x's dtype (vk_fourier_highpass; the plane must fit the workgroup's LDS, ops.fourier_highpass_fits)."""
+    B, Cn, H, W = x.shape
+    keep = fourier_keep_mask_on(x.device, H, W, d_s)
+    return ops.fourier_highpass(x.float().contiguous(), keep, scale).type(x.dtype)
+
+
 def mlp_f32(x_bf16, pw0, pw2):
     """Linear-SiLU-Linear with f32 output (embedding MLPs; video_model.py:148-157,176-182; video_attention.py:227-231)."""
     h = ops.linear(x_bf16, pw0, out_f32=True)

@@ -1684,3 +1684,92 @@ def stroke_overlay(frames, sets, set_of_frame, out=None):
     plan = sets if isinstance(sets, _lib.VkStrokePlan) else stroke_plan(sets)
     check(_lib.load().vk_stroke_overlay_u8(_p(frames), _p(out), _p(set_of_frame), C.byref(plan), n, H, W, _stream()), "vk_stroke_overlay_u8")
     return out
+
+
+# ---- denoising-loss front door (csrc/loss.hip) ----
+LOSS_STATS_BLOCKS, LOSS_MAX_CHANNELS = 16, 64   # VK_LOSS_STATS_BLOCKS, VK_LOSS_MAX_CHANNELS of include/vista_hip.h
+
+
+def _latents4(t, name):
+    _need(t, F32, name)
+    if t.dim() != 4 or not t.is_contiguous():
+        raise ValueError(f"{name}: expected dense (n, C, h, w) fp32 latents, got {tuple(t.shape)} with strides {tuple(t.stride())}")
+
+
+def _per_image(t, name, like, numel):
+    if t is None:
+        return
+    _dense(t, name, F32, like.get_device(), 4, numel)
+
+
+def loss_noise_input(x, noise, sigma, mask=None, offset=None, level=0.0, out=None):
+    """x, noise (n, C, h, w) f32, sigma (n,), mask (n,) or None, offset (n, C) or None -> x + (noise + level * offset) * ((1 - mask) * sigma),
+    bit for bit torch's fp32 expression on the CPU (vk_loss_noise_input). Operands are taken where they lie (16-byte lanes where they allow it);
+    nothing is synchronised."""
+    _latents4(x, "x")
+    _latents4(noise, "noise")
+    if noise.shape != x.shape or noise.device != x.device:
+        raise ValueError(f"loss_noise_input: noise {tuple(noise.shape)} on {noise.device} does not match x {tuple(x.shape)} on {x.device}")
+    n, Cn, h, w = x.shape
+    _per_image(sigma, "sigma", x, n)
+    _per_image(mask, "mask", x, n)
+    _per_image(offset, "offset", x, n * Cn)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _latents4(out, "out")
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError("loss_noise_input: out must have x's shape and device")
+    check(_lib.load().vk_loss_noise_input(_p(x), _p(noise), _p(sigma), _p(mask), _p(offset), float(level), _p(out), n, Cn, h * w, _stream()),
+          "vk_loss_noise_input")
+    return out
+
+
+def fourier_highpass_fits(H, W):
+    """Can vk_fourier_highpass hold an H x W plane (include/vista_hip.h: 16 H W + 16 (H + W) <= 160 KiB)? Pure arithmetic: no library, no GPU."""
+    return H >= 1 and W >= 1 and 16 * H * W + 16 * (H + W) <= 160 * 1024
+
+
+def fourier_highpass(a, keep, scale, b=None, cond_mask=None):
+    """a (n, C, H, W) f32 -> the reference's fourier_filter of every plane of d = a (b None), a - b, or (a * (1 - m) + b * m) - b with
+    m = cond_mask[image] (vk_fourier_highpass). keep (H, W) uint8 on the GPU: 1 where the UNSHIFTED frequency is kept, 0 where it is multiplied
+    by `scale`. Nothing is synchronised."""
+    _latents4(a, "a")
+    n, Cn, H, W = a.shape
+    if b is not None:
+        _latents4(b, "b")
+        if b.shape != a.shape or b.device != a.device:
+            raise ValueError(f"fourier_highpass: b {tuple(b.shape)} on {b.device} does not match a {tuple(a.shape)} on {a.device}")
+    if cond_mask is not None and b is None:
+        raise ValueError("fourier_highpass: cond_mask blends a with b; give b")
+    _per_image(cond_mask, "cond_mask", a, n)
+    _dense(keep, "keep", torch.uint8, a.get_device(), 1, H * W)
+    if not fourier_highpass_fits(H, W):
+        raise OperandError(f"fourier_highpass: a {H} x {W} plane does not fit the workgroup's LDS (16 H W + 16 (H + W) <= 160 KiB; 72 x 128 does)")
+    y = torch.empty_like(a)
+    check(_lib.load().vk_fourier_highpass(_p(a), _p(b), _p(cond_mask), _p(keep), float(scale), _p(y), n * Cn, Cn, H, W, _stream()),
+          "vk_fourier_highpass")
+    return y
+
+
+def loss_stats(out, target, num_frames, cond_mask=None, hf=None, l1=False):
+    """out, target (B * T, C, h, w) f32, T = num_frames -> sums (B * T, 3) float64 on the GPU: per frame S0 = sum e, S1 = sum e * aux_w,
+    S2 = sum |hf|^p (vk_loss_stats; include/vista_hip.h states e, aux_w and the order of the sums). Two launches; nothing is synchronised."""
+    _latents4(out, "out")
+    _latents4(target, "target")
+    if target.shape != out.shape or target.device != out.device:
+        raise ValueError(f"loss_stats: target {tuple(target.shape)} on {target.device} does not match out {tuple(out.shape)} on {out.device}")
+    n, Cn, h, w = out.shape
+    if not isinstance(num_frames, int) or num_frames < 1 or n % num_frames:
+        raise ValueError(f"loss_stats: {n} images are no whole number of clips of {num_frames} frames")
+    if hf is not None:
+        _latents4(hf, "hf")
+        if hf.shape != out.shape or hf.device != out.device:
+            raise ValueError("loss_stats: hf must have out's shape and device")
+    _per_image(cond_mask, "cond_mask", out, n)
+    B = n // num_frames
+    sums = torch.empty((max(n, 1), 3), dtype=torch.float64, device=out.device)[:n]
+    ws = torch.empty(B * Cn * LOSS_STATS_BLOCKS, dtype=torch.float64, device=out.device) if num_frames > 1 else None   # (T == 1: launch 1 is skipped)
+    check(_lib.load().vk_loss_stats(_p(out), _p(target), _p(cond_mask), _p(hf), _p(sums), _p(ws), B, num_frames, Cn, h * w, int(bool(l1)), _stream()),
+          "vk_loss_stats")
+    return sums
