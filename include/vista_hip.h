@@ -393,6 +393,18 @@ int vk_sampler_prepare(float* x, const float* cond_frame, const float* mask, con
  *   halves; g = den_u + scale[t]*(den_c - den_u); d = (x - g)/sigma; x += d*(sigma_next - sigma). */
 int vk_sampler_update(float* x, const float* net_out, const float* scale, int32_t T, int32_t HW, int32_t ld,
                       float c_out, float c_skip, float sigma, float sigma_next, void* stream);
+/* vk_sampler_update_2m: the same step for DPM-Solver++(2M) (Lu et al. 2022; k-diffusion's sample_dpmpp_2m). x, hist f32 [T][4][HW];
+ *   net_out, scale as for vk_sampler_update; g is formed by the same expression. Then x = fmaf(c, hist, fmaf(b, g, a*x)) and hist = g:
+ *   hist carries the guided denoised value to the next step. first != 0: x = fmaf(b, g, a*x); hist is written but never read (it may hold
+ *   anything). The coefficients a, b, c are made on the host in float64 (sampling.dpmpp2m_coefficients): the kernel sees no log, exp or
+ *   division. With (a, b, c) = (0, 1, 0) x becomes g exactly. No atomics; bitwise repeatable.
+ * Operands: x, net_out, scale, hist non-NULL and 4-byte aligned (floats); T, HW > 0; ld >= 4; hist != x. Else VK_EINVAL, before any HIP call. */
+int vk_sampler_update_2m(float* x, const float* net_out, const float* scale, float* hist, int32_t T, int32_t HW, int32_t ld,
+                         float c_out, float c_skip, float a, float b, float c, int32_t first, void* stream);
+/* vk_dpmpp2m_step: the update alone, for a denoiser that is any callable: out = fmaf(c, den_old, fmaf(b, den, a*x)) over n f32 elements;
+ *   den_old NULL: out = fmaf(b, den, a*x). out may be x. Operands: x, den, out non-NULL, every pointer 4-byte aligned, n > 0. Else VK_EINVAL. */
+int vk_dpmpp2m_step(const float* x, const float* den, const float* den_old, float* out, float a, float b, float c, int64_t n,
+                    void* stream);
 
 /* generic pieces of the same maths for callers that use the reference's Denoiser / guider API directly */
 /* out = net*c_out[n] + x*c_skip[n]  (NCHW f32, per-image coefficients; denoiser.py:35) */

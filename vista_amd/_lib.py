@@ -134,6 +134,8 @@ SIGNATURES = {
     "vk_cast_f32_to_bf16": [_vp, _vp, _i64, _vp],
     "vk_sampler_prepare": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp],
     "vk_sampler_update": [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp],
+    "vk_sampler_update_2m": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp],
+    "vk_dpmpp2m_step": [_vp, _vp, _vp, _vp, _f32, _f32, _f32, _i64, _vp],
     "vk_denoiser_combine": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp],
     "vk_cfg_combine": [_vp, _vp, _vp, _i32, _i32, _vp],
     "vk_euler_step": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp],

@@ -153,6 +153,35 @@ __global__ void sampler_update_kernel(float* __restrict__ x, const float* __rest
     }
 }
 
+// DPM-Solver++(2M): x' = a x + b d + c d_old with host-made coefficients (no log / exp / division here). `first`: no history yet -- hist is
+// written, never read. x and hist must not alias (the launcher refuses hist == x); net, scale are read only.
+__global__ void sampler_update_2m_kernel(float* __restrict__ x, const float* __restrict__ net, const float* __restrict__ scale,
+                                         float* __restrict__ hist, int T, int HW, int ld, float c_out, float c_skip, float a, float b, float c2,
+                                         int first) {
+    const long long n = (long long)T * 4 * HW;
+    GRID_STRIDE(i, n) {
+        const int pix = (int)(i % HW);
+        const long long ic = i / HW;
+        const int c = (int)(ic % 4);
+        const int t = (int)(ic / 4);
+        const float xv = x[i];
+        const float du = net[((size_t)t * HW + pix) * ld + c] * c_out + xv * c_skip;
+        const float dc = net[((size_t)(T + t) * HW + pix) * ld + c] * c_out + xv * c_skip;
+        const float g = du + scale[t] * (dc - du);
+        const float v = fmaf(b, g, a * xv);
+        x[i] = first ? v : fmaf(c2, hist[i], v);
+        hist[i] = g;
+    }
+}
+// the same update where the denoised tensors exist (generic path); out may be x (each element is read before it is written, by its own thread)
+__global__ void dpmpp2m_step_kernel(const float* x, const float* __restrict__ den, const float* __restrict__ den_old, float* out, float a,
+                                    float b, float c2, long long n) {
+    GRID_STRIDE(i, n) {
+        const float v = fmaf(b, den[i], a * x[i]);
+        out[i] = den_old ? fmaf(c2, den_old[i], v) : v;
+    }
+}
+
 __global__ void denoiser_combine_kernel(const float* __restrict__ net, const float* __restrict__ x, const float* __restrict__ c_out,
                                         const float* __restrict__ c_skip, float* __restrict__ out, int n_img, int chw) {
     const long long n = (long long)n_img * chw;
@@ -357,6 +386,17 @@ extern "C" int vk_sampler_update(float* x, const float* net_out, const float* sc
                                  float c_skip, float sigma, float sigma_next, void* stream) {
     if (!x || !net_out || !scale || T <= 0 || HW <= 0 || ld < 4 || sigma == 0.f || !aligned_to(x, 4) || !aligned_to(net_out, 4) || !aligned_to(scale, 4)) return VK_EINVAL;
     EW_LAUNCH(sampler_update_kernel, (long long)T * 4 * HW, x, net_out, scale, T, HW, ld, c_out, c_skip, sigma, sigma_next);
+}
+extern "C" int vk_sampler_update_2m(float* x, const float* net_out, const float* scale, float* hist, int32_t T, int32_t HW, int32_t ld,
+                                    float c_out, float c_skip, float a, float b, float c, int32_t first, void* stream) {
+    if (!x || !net_out || !scale || !hist || T <= 0 || HW <= 0 || ld < 4 || hist == x) return VK_EINVAL;
+    if (!aligned_to(x, 4) || !aligned_to(net_out, 4) || !aligned_to(scale, 4) || !aligned_to(hist, 4)) return VK_EINVAL;
+    EW_LAUNCH(sampler_update_2m_kernel, (long long)T * 4 * HW, x, net_out, scale, hist, T, HW, ld, c_out, c_skip, a, b, c, first);
+}
+extern "C" int vk_dpmpp2m_step(const float* x, const float* den, const float* den_old, float* out, float a, float b, float c, int64_t n,
+                               void* stream) {
+    if (!x || !den || !out || n <= 0 || !aligned_to(x, 4) || !aligned_to(den, 4) || !aligned_to(den_old, 4) || !aligned_to(out, 4)) return VK_EINVAL;
+    EW_LAUNCH(dpmpp2m_step_kernel, (long long)n, x, den, den_old, out, a, b, c, (long long)n);
 }
 extern "C" int vk_denoiser_combine(const float* net, const float* x, const float* c_out, const float* c_skip, float* out, int32_t n_img,
                                    int32_t chw, void* stream) {

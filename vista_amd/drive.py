@@ -128,10 +128,10 @@ class DriveSession:
     cond_aug noise, build the sampler) and encodes the pictures; `step(action)` samples one round. Noise comes from torch's global generator at
     step time, in do_sample's order; that the pictures are encoded before round 0's conditioning instead of after it changes nothing as long
     as the conditioner draws nothing from the generator (the shipped one encodes with the posterior's mode). Graph replay and concurrent guidance
-    halves are on unless `eager`, as in sample.run."""
+    halves are on unless `eager`, as in sample.run. `sampler`: as in sample.run (None = the environment hook VISTA_SAMPLER)."""
 
     def __init__(self, model, frame_list, *, height=576, width=1024, n_frames=25, n_conds=1, n_steps=50, cfg_scale=2.5, cond_aug=0.0, eager=False,
-                 guider="TrianglePredictionGuider"):
+                 guider="TrianglePredictionGuider", sampler=None):
         import torch
         self.model, self.n_frames, self.cond_aug = model, n_frames, cond_aug
         self.guider, self.cfg_scale = guider, cfg_scale   # (what vista_amd.plan builds its scoring sampler from)
@@ -139,7 +139,8 @@ class DriveSession:
         cond_img = self.inputs[:1]
         self._cond_frames = cond_img + cond_aug * torch.randn_like(cond_img)
         self._scalars = SU.init_embedder_options(set(e.input_key for e in model.conditioner.embedders))
-        self.sampler = SU.init_sampling(guider=guider, steps=n_steps, cfg_scale=cfg_scale, num_frames=n_frames)
+        self.sampler_name = SU.sampler_name(sampler)   # (None: the environment hook VISTA_SAMPLER, read once: the session and its forks keep it)
+        self.sampler = SU.init_sampling(sampler=self.sampler_name, guider=guider, steps=n_steps, cfg_scale=cfg_scale, num_frames=n_frames)
         self.sampler.graph = self.sampler.cfg_streams = not eager
         self._denoiser = SU.rollout_denoiser(model)
         with torch.no_grad(), model.ema_scope("Sampling"):
@@ -343,6 +344,7 @@ def plan_run(opt, argv=None, net_params=None):
         entries = ["scene"] * opt.n_rounds
     check_world()
     SU.check_sizes(opt.height, opt.width, opt.n_frames, len(entries), opt.n_conds, net_params)
+    SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     return entries
 
 

@@ -10,6 +10,9 @@ including its in-place scaling of the caller's `x` (sampling.py:36). Two executi
               and the EDM coefficients live on the host as floats (no per-step device sync: the reference syncs twice
               per step, sampling.py:109 and video_model.py:457), the UNet is entered token-major, and the step's
               elementwise work is two kernels (vk_sampler_prepare, vk_sampler_update).
+
+DPMPP2MSampler (end of the file; not in the reference) is DPM-Solver++(2M) with the same `__call__` and the same two paths: FusedLoop2M swaps
+the step's last kernel for vk_sampler_update_2m, the generic path ends in vk_dpmpp2m_step.
 """
 import os
 from typing import Dict, Union
@@ -311,9 +314,99 @@ class FusedLoop:
             tl = self.xw.shape[0]
             mine = self._unet(net_in[self.half * tl:(self.half + 1) * tl], self.n, c_noise)
             net_out = self.shard.exchange_cfg_halves(mine)
+        self._update(i, net_out, c_out, c_skip)
+
+    def _update(self, i, net_out, c_out, c_skip):
+        """The step's last kernel, outside the UNet graph: guider combine -> to_d -> Euler update. A subclass swaps the update (FusedLoop2M)."""
         ops.sampler_update(self.xw, net_out, self.scales, c_out, c_skip, self.sig[i], self.sig[i + 1])
 
     def finish(self):
         if self.replace:
             self.xw = ops.mask_replace(self.xw, self.cf, self.maskf)
         return self.xw if self.shard is None else self.shard.gather_frames(self.xw)
+
+
+# ---- DPM-Solver++(2M) ------------------------------------------------------------------------------------------------------------------------
+def dpmpp2m_coefficients(sigmas):
+    """The schedule's (a, b, c) per step, as Python floats (float64; the kernels take them rounded to fp32), so that a step is
+        x' = a x + b D(x, sigma_i) + c D_old        (D_old: the denoised value of the step before)
+    -- DPM-Solver++(2M) (Lu et al. 2022) in the form of k-diffusion's sample_dpmpp_2m, first-order first and final steps. With t = -ln sigma,
+    h = t_next - t = ln(sigma / sigma_next) and r = h_prev / h:  a = sigma_next / sigma,  e = -expm1(-h) (= 1 - a),  b = e (1 + 1 / (2 r)),
+    c = -e / (2 r); the first step has b = e, c = 0; the step onto sigma_next = 0 is (0, 1, 0): x' is the denoised value itself. GPU-free."""
+    import math
+    sig = [float(s) for s in sigmas]
+    out, h_prev = [], None
+    for s, s_next in zip(sig[:-1], sig[1:]):
+        if s_next == 0.0:
+            out.append((0.0, 1.0, 0.0))
+            h_prev = None
+            continue
+        h = math.log(s) - math.log(s_next)
+        e = -math.expm1(-h)
+        if h_prev is None:
+            b, c = e, 0.0
+        else:
+            r = h_prev / h
+            b, c = e * (1.0 + 1.0 / (2.0 * r)), -e / (2.0 * r)
+        out.append((s_next / s, b, c))
+        h_prev = h
+    return out
+
+
+class FusedLoop2M(FusedLoop):
+    """FusedLoop with the Euler update swapped for vk_sampler_update_2m: the same prepare kernel, the same UNet forward (eager, graph replay,
+    concurrent halves -- and the same graph cache and key: the update is outside the graph), and a persistent `hist` of xw's shape (a frame
+    shard's local frames, like xw) that carries the guided denoised value from one step to the next."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.coef2m = dpmpp2m_coefficients(self.sig)   # host, float64, once per run
+        self.hist = torch.empty_like(self.xw)          # written by every step, first read by the second
+
+    def _update(self, i, net_out, c_out, c_skip):
+        a, b, c = self.coef2m[i]
+        # c == 0: the first step (no history yet) and the final one (x' = the denoised value): hist is written, not read
+        ops.sampler_update_2m(self.xw, net_out, self.scales, self.hist, c_out, c_skip, a, b, c, first=(c == 0.0))
+
+
+class DPMPP2MSampler(BaseDiffusionSampler):
+    """DPM-Solver++(2M): one denoiser evaluation per step like EulerEDMSampler, second order through the previous step's denoised value. No churn.
+    `__call__` is EulerEDMSampler's: the caller's x is scaled in place, cond_frame / cond_mask replacement before every step and after the loop,
+    `graph` / `cfg_streams` / `shard` mean the same, and the same two paths (generic: ops.dpmpp2m_step on the guider's output; fused:
+    FusedLoop2M). Not in the reference, which ships the first-order sampler only."""
+
+    def __init__(self, discretization_config, num_steps=None, guider_config=None, verbose=False, device="cuda"):
+        super().__init__(discretization_config, num_steps=num_steps, guider_config=guider_config, verbose=verbose, device=device)
+        self.graph = None
+        self.cfg_streams = None
+
+    @torch.no_grad()
+    def __call__(self, denoiser, x, cond, uc=None, cond_frame=None, cond_mask=None, num_steps=None):
+        x, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
+        sig = [float(s) for s in sigmas]
+        replace = cond_mask is not None and cond_frame is not None and bool(cond_mask.detach().cpu().any())
+        if cond_mask is None:
+            cond_mask = torch.zeros(x.shape[0], device=x.device)
+        maskf = cond_mask.float().contiguous()
+        if isinstance(denoiser, FusedDenoiser) and not isinstance(self.guider, IdentityGuider) \
+                and EulerEDMSampler._fused_layout_ok(denoiser, x, cond, uc):
+            loop = FusedLoop2M(self, denoiser, x.float().clone(), cond, uc, cond_frame, maskf, replace, sig, shard=getattr(self, "shard", None),
+                               graph=self.graph, cfg_streams=self.cfg_streams)
+            for i in range(len(sig) - 1):
+                loop.step(i)
+            return loop.finish().to(x.dtype)
+        n = x.shape[0]
+        xw = x.float().contiguous()
+        coef = dpmpp2m_coefficients(sig)
+        old = None   # the previous step's denoised tensor, kept by reference
+        for i in range(num_sigmas - 1):
+            if replace:
+                xw = ops.mask_replace(xw, cond_frame.float(), maskf)
+            s_cur = torch.full((n,), sig[i], device=x.device)
+            denoised = self.denoise(xw, denoiser, s_cur, cond, maskf, uc).float().contiguous()
+            a, b, c = coef[i]
+            xw = ops.dpmpp2m_step(xw, denoised, old if c != 0.0 else None, a, b, c)
+            old = denoised
+        if replace:
+            xw = ops.mask_replace(xw, cond_frame.float(), maskf)
+        return xw.to(x.dtype)

@@ -1348,6 +1348,44 @@ def sampler_update(x, net_out, scale, c_out, c_skip, sigma, sigma_next):
     return x
 
 
+def sampler_update_2m(x, net_out, scale, hist, c_out, c_skip, a, b, c, first):
+    """The fused DPM-Solver++(2M) step (vk_sampler_update_2m): x = fmaf(c, hist, fmaf(b, g, a*x)) and hist = g, both in place. `first`: hist is
+    written but not read. (a, b, c): one triple of sampling.dpmpp2m_coefficients."""
+    T, ch, H, W = x.shape
+    if ch != 4:
+        _refuse("x", x, "must be (T, 4, H, W)")
+    _dense(x, "x", F32, x.get_device(), 4, T * 4 * H * W)
+    _token_rows(net_out, "net_out", F32, x.get_device(), 4, 2 * T * H * W, 4)
+    _dense(scale, "scale", F32, x.get_device(), 4, T)
+    if tuple(hist.shape) != tuple(x.shape):
+        _refuse("hist", hist, f"must have x's shape {tuple(x.shape)}")
+    _dense(hist, "hist", F32, x.get_device(), 4, T * 4 * H * W)
+    if hist.data_ptr() == x.data_ptr():
+        _refuse("hist", hist, "must not be x: the step reads x and writes both")
+    check(_lib.load().vk_sampler_update_2m(_p(x), _p(net_out), _p(scale), _p(hist), T, H * W, net_out.stride(-2), float(c_out), float(c_skip),
+                                           float(a), float(b), float(c), 1 if first else 0, _stream()), "vk_sampler_update_2m")
+    return x
+
+
+def dpmpp2m_step(x, den, den_old, a, b, c, out=None):
+    """out = fmaf(c, den_old, fmaf(b, den, a*x)) (vk_dpmpp2m_step); den_old None: fmaf(b, den, a*x). A new tensor unless out= is given (out may be x)."""
+    dev, n = x.get_device(), x.numel()
+    _dense(x, "x", F32, dev, 4, n)
+    for name, t in (("den", den), ("den_old", den_old)):
+        if t is not None:
+            if tuple(t.shape) != tuple(x.shape):
+                _refuse(name, t, f"must have x's shape {tuple(x.shape)}")
+            _dense(t, name, F32, dev, 4, n)
+    if out is None:
+        out = torch.empty(x.shape, dtype=F32, device=x.device)
+    else:
+        if tuple(out.shape) != tuple(x.shape):
+            _refuse("out", out, f"must have x's shape {tuple(x.shape)}")
+        _dense(out, "out", F32, dev, 4, n)
+    check(_lib.load().vk_dpmpp2m_step(_p(x), _p(den), _p(den_old), _p(out), float(a), float(b), float(c), n, _stream()), "vk_dpmpp2m_step")
+    return out
+
+
 def _c(*ts):
     return [t.contiguous() for t in ts]
 

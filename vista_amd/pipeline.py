@@ -42,7 +42,23 @@ def get_guider(guider="LinearPredictionGuider", cfg_scale=2.5, num_frames=25):
     raise NotImplementedError(f"unknown guider {guider!r}")
 
 
+SAMPLERS = ("EulerEDMSampler", "DPMPP2MSampler")   # the reference ships the first; the second (DPM-Solver++(2M)) is this package's
+
+
+def sampler_name(sampler=None):
+    """The sampler a front door builds: `sampler` if given, else the environment hook VISTA_SAMPLER, else EulerEDMSampler (the reference's).
+    The one place the hook is read. A name that is not built is refused here, by name, before a model is built."""
+    name = sampler if sampler is not None else (os.environ.get("VISTA_SAMPLER") or "EulerEDMSampler")
+    if name not in SAMPLERS:
+        where = " (environment hook VISTA_SAMPLER)" if sampler is None else ""
+        raise ValueError(f"Unknown sampler {name}{where}: one of {', '.join(SAMPLERS)}")
+    return name
+
+
 def get_sampler(sampler, steps, discretization_config, guider_config):
+    if sampler == "DPMPP2MSampler":
+        from .modules.diffusionmodules.sampling import DPMPP2MSampler
+        return DPMPP2MSampler(num_steps=steps, discretization_config=discretization_config, guider_config=guider_config, verbose=False)
     if sampler != "EulerEDMSampler":
         raise ValueError(f"Unknown sampler {sampler}")
     from .modules.diffusionmodules.sampling import EulerEDMSampler

@@ -84,12 +84,13 @@ def require_best(scores, r, where=None):
 class Planner:
     """Scores candidate actions for the next round of a DriveSession and steps it under the best. The scoring sampler has `score_steps` steps
     and the session's guider, cfg_scale and -- unless `eager` says otherwise -- graph settings; the UNet's captured graphs are keyed by the
-    window's geometry, so the graphs the session's sampler captured serve this one as well."""
+    window's geometry, so the graphs the session's sampler captured serve this one as well. `sampler`: the scoring sampler's class, as in
+    sample.run (None = the environment hook VISTA_SAMPLER)."""
 
-    def __init__(self, session, *, ens_size=5, score_steps=10, score_seed=0, eager=None):
+    def __init__(self, session, *, ens_size=5, score_steps=10, score_seed=0, eager=None, sampler=None):
         check_ensemble(ens_size, score_steps)
         self.session, self.ens_size, self.score_steps, self.score_seed = session, ens_size, score_steps, score_seed
-        self.sampler = SU.init_sampling(guider=session.guider, steps=score_steps, cfg_scale=session.cfg_scale, num_frames=session.n_frames)
+        self.sampler = SU.init_sampling(sampler=SU.sampler_name(sampler), guider=session.guider, steps=score_steps, cfg_scale=session.cfg_scale, num_frames=session.n_frames)
         graph = bool(session.sampler.graph) if eager is None else not eager
         self.sampler.graph = self.sampler.cfg_streams = graph
 
@@ -213,6 +214,7 @@ def plan_run(opt, argv=None, net_params=None):
         raise ValueError("--" + str(e)) from None
     check_world()
     SU.check_sizes(opt.height, opt.width, opt.n_frames, len(rounds), opt.n_conds, net_params)
+    SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     return rounds
 
 

@@ -97,14 +97,14 @@ def scene_candidates(selected_index, dataset, n_frames, names, data_root=None, a
 
 
 def run(model, frame_list, action_dicts, *, height=576, width=1024, n_frames=25, n_conds=1, n_steps=10, cfg_scale=2.5, cond_aug=0.0,
-        ens_size=5, eager=False, want_map=False, members=None, comm=None, timings=None, inputs_out=None):
+        ens_size=5, eager=False, want_map=False, members=None, comm=None, timings=None, inputs_out=None, sampler=None):
     """One scene of the reference's loop (reward.py:214-250) under every candidate of `action_dicts` (a list of action dicts; {} or None = no
     action) -> [RewardReport], one per candidate. Mirrors sample.run: load and resize the frames, one value dict per candidate (the
     conditioning frame and its augmentation noise are shared), VanillaCFG, reward_utils.estimate. The sampler replays the UNet of a step from a
     captured hipGraph, the guidance halves concurrently, unless `eager`: the graphs captured for the first member are the ones every later
     member and candidate replays. The caller seeds. `members` / `comm`: see reward_utils.estimate. `timings` (a dict) receives the wall time
     in seconds of load, condition, encode and sample (= the rest: ens_size x n_steps denoising steps per candidate and the statistics).
-    `inputs_out` (a list) receives the loaded frames, (n_frames, 3, height, width) in [-1, 1]."""
+    `inputs_out` (a list) receives the loaded frames, (n_frames, 3, height, width) in [-1, 1]. `sampler`: as in sample.run (None = VISTA_SAMPLER)."""
     t0 = time.perf_counter()
     images = SU.load_img_seq(frame_list, height, width, "cuda")
     torch.cuda.synchronize()
@@ -120,7 +120,7 @@ def run(model, frame_list, action_dicts, *, height=576, width=1024, n_frames=25,
         value_dict = dict(base)
         value_dict.update(action or {})
         value_dicts.append(value_dict)
-    sampler = SU.init_sampling(guider="VanillaCFG", steps=n_steps, cfg_scale=cfg_scale, num_frames=n_frames)
+    sampler = SU.init_sampling(sampler=SU.sampler_name(sampler), guider="VanillaCFG", steps=n_steps, cfg_scale=cfg_scale, num_frames=n_frames)
     sampler.graph = sampler.cfg_streams = not eager
     stages = {}
     with (_StageClock(model, stages) if timings is not None else contextlib.nullcontext()):
@@ -213,6 +213,7 @@ def main(argv=None):
     # what cannot run is refused here, before 2.5 billion parameters are built
     net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
     SU.check_sizes(opt.height, opt.width, opt.n_frames, 1, opt.n_conds, net_params)
+    SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     if opt.ens_size < 2:
         raise ValueError(f"--ens_size {opt.ens_size}: reward estimation needs at least two ensemble members (unbiased variance)")
     if opt.heat_max is not None and not opt.heat_max > 0.0:

@@ -99,14 +99,15 @@ class _StageClock:
 
 
 def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames=25, n_rounds=1, n_conds=1, n_steps=50, cfg_scale=2.5,
-        cond_aug=0.0, eager=False, timings=None, shard=None):
+        cond_aug=0.0, eager=False, timings=None, shard=None, sampler=None):
     """One sample of the reference's loop (sample.py:222-254) without the files -> (samples in [0, 1], samples_z, inputs in [-1, 1]): load and
     resize the frames, build the value dict, pick the guider (TrianglePredictionGuider for a rollout, VanillaCFG for one round), do_sample.
     The caller seeds. `timings` (a dict) receives the wall time in seconds of load, condition, encode, decode and sample (= the rest of do_sample:
     the denoising loops).
     `shard` (a vista_amd.parallel.FrameShard, one per rank, every rank calling with the same arguments and the same seed): the denoising steps
     run frame-sharded over the shard's ranks, eagerly on one stream whatever `eager` says (a captured graph cannot hold the collectives: DESIGN
-    section 6). Conditioner, encoder, decoder and the noise are replicated: every rank returns the same tensors."""
+    section 6). Conditioner, encoder, decoder and the noise are replicated: every rank returns the same tensors.
+    `sampler`: "EulerEDMSampler" | "DPMPP2MSampler"; None = the environment hook VISTA_SAMPLER, unset = EulerEDMSampler (SU.sampler_name)."""
     t0 = time.perf_counter()
     images = SU.load_img_seq(frame_list, height, width, "cuda")
     torch.cuda.synchronize()
@@ -119,8 +120,8 @@ def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames
     value_dict["cond_frames"] = cond_img + cond_aug * torch.randn_like(cond_img)
     for key, value in (action_dict or {}).items():
         value_dict[key] = value
-    sampler = SU.init_sampling(guider="TrianglePredictionGuider" if n_rounds > 1 else "VanillaCFG", steps=n_steps, cfg_scale=cfg_scale,
-                               num_frames=n_frames)
+    sampler = SU.init_sampling(sampler=SU.sampler_name(sampler), guider="TrianglePredictionGuider" if n_rounds > 1 else "VanillaCFG", steps=n_steps,
+                               cfg_scale=cfg_scale, num_frames=n_frames)
     sampler.graph = sampler.cfg_streams = not eager and shard is None   # (graph replay: one GPU, no frame shard)
     if shard is not None:
         sampler.shard = shard
@@ -181,6 +182,7 @@ def main(argv=None):
     # sizes the kernels cannot take are refused here, before 2.5 billion parameters are built
     net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
     SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, net_params)
+    SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:   # one rank of a torch.distributed.run job
         rank, shard = init_distributed(opt.n_frames)
         try:
