@@ -676,6 +676,48 @@ int vk_fourier_highpass(const float* a, const float* b, const float* cond_mask, 
 int vk_loss_stats(const float* out, const float* target, const float* cond_mask, const float* hf, double* sums, double* partial_ws, int32_t B,
                   int32_t T, int32_t C, int32_t hw, int32_t l1, void* stream);
 
+/* ------------------------------------------------------------------ Motion-JPEG video output (csrc/jpeg.hip)
+ * Added under ABI v9 without a version step, as the reward, evaluation, planning and loss entry points were: purely additive. uint8 in, int16 and
+ * bytes out, storage-type independent: the same code is linked into both libraries.
+ * A baseline sequential JPEG (ITU-T T.81): 8 bit, three components, 4:2:0 (MCU = 16 x 16 pixels = blocks Y00 Y01 Y10 Y11 Cb Cr), the Annex K
+ * "typical" Huffman tables, one restart interval per MCU row. mcu_h = ceil(H / 16), mcu_w = ceil(W / 16). The headers are the host's.
+ *
+ * vk_jpeg_dct_quant_u8: frames (n, H, W, 3) uint8 -> coef (n, 6 * mcu_h * mcu_w, 64) int16: per block the quantised coefficients in zigzag order,
+ * blocks in scan order (MCUs row-major). In fp32: Y = 0.299 R + 0.587 G + 0.114 B, Cb = -0.168736 R - 0.331264 G + 0.5 B + 128,
+ * Cr = 0.5 R - 0.418688 G - 0.081312 B + 128, nothing rounded to 8 bit; frames padded to whole MCUs by edge replication; a chroma sample is the
+ * mean of its 2 x 2 unrounded samples; level shift by -128; the orthonormal 8 x 8 DCT-II of A.3.3 (rows, then columns); division by the
+ * quantiser, rounded half away from zero; DC clamped to [-1024, 1023], AC to [-1023, 1023].
+ *   quant  HOST memory, read during the call, handed to the kernel by value: `quality` (1 .. 100, the libjpeg rule the tables were scaled by; the
+ *          kernel does not read it) and the two tables in ZIGZAG order, every entry 1 .. 255.
+ *   Operands: frames dense, any alignment -- the copy into LDS moves 16 bytes per lane where 3 W % 16 == 0 and frames is 16-byte aligned, 4 where
+ *   3 W % 4 == 0 and it is 4-byte aligned, else bytes; the coefficients are the same on every path. coef dense, 16-byte aligned (16-byte stores).
+ *   1 <= H, W <= 65535, n >= 1, 6 n mcu_h mcu_w (the block count) and 3 n H W (the frames' bytes) at most 2^31 - 1.
+ *   VK_EINVAL, before any HIP call: a NULL pointer, an extent outside those limits, coef misaligned, quality outside 1 .. 100, a table entry
+ *   outside 1 .. 255.
+ *
+ * vk_jpeg_interval_sizes: sizes[n * mcu_h] int32 = the bytes of every restart interval's entropy-coded data: byte stuffing (0xFF -> 0xFF 0x00)
+ * included, the last partial byte padded with 1-bits, plus 2 for the RSTm marker that follows every interval but a frame's last.
+ * vk_jpeg_entropy_write: writes interval i at out + offsets[i] (int64, DEVICE memory; the caller's exclusive sum of the sizes, so that one frame's
+ * scan is one contiguous slice), followed by RSTm (0xFF, 0xD0 + MCU row % 8) where it has one. Every byte of [offsets[i], offsets[i] + sizes[i])
+ * is stored exactly once by a plain store and no other byte is touched: out need not be zeroed. A byte that would fall outside [0, out_bytes) is
+ * not stored. Both run the same code, one workgroup per interval; integer operations only, bitwise repeatable.
+ *   The DC difference of a block is taken against the previous block of its component in scan order, the predictor is 0 at each interval's
+ *   start. A coefficient outside the ranges above is replaced by the nearest value inside them before anything else (as a DC value, as a
+ *   predictor and as an AC value alike): the stream is that of the clamped array.
+ *   blocks  the block count of coef, stated by the caller: it must equal 6 n mcu_h mcu_w.
+ *   Operands: coef dense, 16-byte aligned (16-byte loads); sizes 4-byte, offsets 8-byte aligned; out any alignment.
+ *   n >= 1, 1 <= mcu_h, mcu_w <= 4096, blocks <= 2^31 - 1, 1 <= out_bytes <= 2^31 - 1.
+ *   VK_EINVAL, before any HIP call: a NULL pointer, an extent outside those limits, blocks != 6 n mcu_h mcu_w, a misaligned coef / sizes / offsets. */
+typedef struct VkJpegQuant {
+    int32_t quality, reserved;
+    uint16_t luma[64];
+    uint16_t chroma[64];
+} VkJpegQuant;
+int vk_jpeg_dct_quant_u8(const void* frames, void* coef, const VkJpegQuant* quant /* HOST memory */, int32_t n, int32_t H, int32_t W, void* stream);
+int vk_jpeg_interval_sizes(const void* coef, int32_t* sizes, int32_t n, int32_t mcu_h, int32_t mcu_w, int32_t blocks, void* stream);
+int vk_jpeg_entropy_write(const void* coef, const int64_t* offsets, void* out, int64_t out_bytes, int32_t n, int32_t mcu_h, int32_t mcu_w,
+                          int32_t blocks, void* stream);
+
 /* library info */
 int vk_abi_version(void);
 /* ABI v7: the 16-bit storage type this library was built for: 0 = bf16 (libvista_hip.so, the default and the BASELINE config's dtype), 1 = IEEE fp16

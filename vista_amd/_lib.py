@@ -89,6 +89,10 @@ class VkStrokePlan(C.Structure):
                 ("stroke", VkStroke * VK_OVERLAY_MAX_STROKES), ("seg", VkStrokeSegment * VK_OVERLAY_MAX_SEGMENTS)]
 
 
+class VkJpegQuant(C.Structure):
+    _fields_ = [("quality", _i32), ("reserved", _i32), ("luma", C.c_uint16 * 64), ("chroma", C.c_uint16 * 64)]
+
+
 ABI_VERSION = 9  # vk_abi_version() of the library this table mirrors
 
 # name -> argtypes; every entry returns int. Must list every symbol include/vista_hip.h declares
@@ -156,6 +160,9 @@ SIGNATURES = {
     "vk_fourier_highpass_lds_bytes": [_i32, _i32],
     "vk_fourier_highpass": [_vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _vp],
     "vk_loss_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "vk_jpeg_dct_quant_u8": [_vp, _vp, C.POINTER(VkJpegQuant), _i32, _i32, _i32, _vp],
+    "vk_jpeg_interval_sizes": [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "vk_jpeg_entropy_write": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
     "vk_abi_version": [],
     "vk_act_dtype": [],
 }

@@ -345,6 +345,7 @@ def plan_run(opt, argv=None, net_params=None):
     check_world()
     SU.check_sizes(opt.height, opt.width, opt.n_frames, len(entries), opt.n_conds, net_params)
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
+    SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
     return entries
 
 
@@ -419,7 +420,7 @@ def _drive_loop(opt, entries, step_rounds=_step_entries, records_name="drive.jso
             hud = draw_hud(ops.frames_to_u8(samples.float()), session.actions, opt.n_frames)
             folder = os.path.join(opt.save, "hud", "videos")
             os.makedirs(folder, exist_ok=True)
-            SU.save_video(os.path.join(folder, f"{opt.dataset}_{sample_index:06}"), hud.cpu().numpy(), 10)
+            SU.save_video(os.path.join(folder, f"{opt.dataset}_{sample_index:06}"), hud, 10)
             timings["hud"] = clock() - t4
         record = make_record(sample_index, frame_list, stepped, seed=opt.seed, action=opt.action, n_frames=opt.n_frames, timings=timings)
         for round_record, extra in zip(record["rounds"], extras or ()):

@@ -46,6 +46,7 @@ def check_run(opt, net_params=None):
     """Refuses, by name and before any model is built, what an evaluation run cannot do."""
     SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, net_params)
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
+    SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
     if opt.height < fidelity.TAPS or opt.width < fidelity.TAPS:
         raise ValueError(f"--height {opt.height} --width {opt.width}: SSIM takes an {fidelity.TAPS} x {fidelity.TAPS} window")
     if opt.dataset == "IMG":

@@ -1811,3 +1811,78 @@ def loss_stats(out, target, num_frames, cond_mask=None, hf=None, l1=False):
     check(_lib.load().vk_loss_stats(_p(out), _p(target), _p(cond_mask), _p(hf), _p(sums), _p(ws), B, num_frames, Cn, h * w, int(bool(l1)), _stream()),
           "vk_loss_stats")
     return sums
+
+
+# ---- Motion-JPEG video output (csrc/jpeg.hip) ----
+JPEG_MAX_EXTENT, JPEG_MAX_COUNT = 65535, 2 ** 31 - 1   # the extent limits include/vista_hip.h states beside the three prototypes
+
+
+def _jpeg_operand(t, name, dtype, ndim, last, align):
+    """An operand of the JPEG entry points: a dense `ndim`-D tensor of `dtype` on a GPU whose last extent is `last`, base address a multiple of
+    `align` bytes. Refused by name, never cloned."""
+    if not torch.is_tensor(t):
+        raise OperandError(f"{name}: expected a torch tensor, got {type(t).__name__}")
+    if t.dtype is dtype and t.is_cuda and t.dim() == ndim and t.shape[-1] == last and t.is_contiguous() and (t.data_ptr() & (align - 1)) == 0:
+        return
+    rule = (f"dtype must be {dtype}" if t.dtype is not dtype else "must be on the GPU (no CPU fallback)" if not t.is_cuda
+            else f"must be {ndim}-D with a last extent of {last}" if t.dim() != ndim or t.shape[-1] != last
+            else "must be dense (contiguous)" if not t.is_contiguous() else f"base address must be a multiple of {align} bytes")
+    raise OperandError(f"{name}: {rule} (got {tuple(t.shape)} {t.dtype} on {t.device}, strides {tuple(t.stride())}, address % 16 = {t.data_ptr() & 15})")
+
+
+def jpeg_quant(quality):
+    """The VkJpegQuant of a quality: libjpeg's scaling of the Annex K tables (video.jpeg_tables), in zigzag order."""
+    from . import video
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise OperandError(f"quality: a JPEG quality is an integer from 1 to 100, got {quality!r}")
+    luma, chroma = video.jpeg_tables(quality)["quant"]
+    q = _lib.VkJpegQuant()
+    q.quality = quality
+    for k, nat in enumerate(video.ZIGZAG):
+        q.luma[k], q.chroma[k] = luma[nat], chroma[nat]
+    return q
+
+
+def jpeg_dct_quant(frames, quality):
+    """frames (n, H, W, 3) uint8, dense, on the GPU (what frames_to_u8, heat_overlay_u8 and stroke_overlay write) -> coef (n, 6 * mcu_h * mcu_w, 64)
+    int16: the quantised DCT coefficients of a 4:2:0 baseline JPEG at `quality`, zigzag order, blocks in scan order (vk_jpeg_dct_quant_u8).
+    Nothing is synchronised."""
+    _jpeg_operand(frames, "frames", torch.uint8, 4, 3, 1)
+    n, H, W, _ = frames.shape
+    if not (n >= 1 and 1 <= H <= JPEG_MAX_EXTENT and 1 <= W <= JPEG_MAX_EXTENT):
+        raise OperandError(f"frames: n >= 1 and 1 <= H, W <= {JPEG_MAX_EXTENT}, got {tuple(frames.shape)}")
+    q = jpeg_quant(quality)
+    mcu_h, mcu_w = (H + 15) // 16, (W + 15) // 16
+    if 6 * n * mcu_h * mcu_w > JPEG_MAX_COUNT or 3 * n * H * W > JPEG_MAX_COUNT:
+        raise OperandError(f"frames: {tuple(frames.shape)} is {6 * n * mcu_h * mcu_w} blocks and {3 * n * H * W} bytes; both must stay below 2^31 "
+                           "(encode fewer frames per call)")
+    coef = torch.empty((n, 6 * mcu_h * mcu_w, 64), dtype=torch.int16, device=frames.device)
+    check(_lib.load().vk_jpeg_dct_quant_u8(_p(frames), _p(coef), C.byref(q), n, H, W, _stream()), "vk_jpeg_dct_quant_u8")
+    return coef
+
+
+def jpeg_entropy(coef, mcu_h, mcu_w):
+    """coef (n, 6 * mcu_h * mcu_w, 64) int16 from jpeg_dct_quant -> (scan, offsets): `scan` a uint8 GPU tensor that holds every frame's
+    entropy-coded scan back to back, `offsets` the n * mcu_h + 1 exclusive byte offsets of the restart intervals as a CPU int64 tensor (frame i is
+    scan[offsets[i * mcu_h] : offsets[(i + 1) * mcu_h]]). vk_jpeg_interval_sizes, a cumulative sum, ONE transfer of the offsets to the host (the
+    only synchronisation: the output's size is data), vk_jpeg_entropy_write."""
+    _jpeg_operand(coef, "coef", torch.int16, 3, 64, 16)
+    for name, v in (("mcu_h", mcu_h), ("mcu_w", mcu_w)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 4096:
+            raise OperandError(f"{name}: a whole number of MCUs from 1 to 4096, got {v!r}")
+    n, blocks, _ = coef.shape
+    if n < 1 or blocks != 6 * mcu_h * mcu_w or n * blocks > JPEG_MAX_COUNT:
+        raise OperandError(f"coef: {tuple(coef.shape)} does not hold n >= 1 frames of 6 * {mcu_h} * {mcu_w} = {6 * mcu_h * mcu_w} blocks "
+                           "(and at most 2^31 - 1 blocks in all)")
+    lib = _lib.load()
+    sizes = torch.empty(n * mcu_h, dtype=torch.int32, device=coef.device)
+    check(lib.vk_jpeg_interval_sizes(_p(coef), _p(sizes), n, mcu_h, mcu_w, n * blocks, _stream()), "vk_jpeg_interval_sizes")
+    offsets = torch.zeros(n * mcu_h + 1, dtype=torch.int64, device=coef.device)
+    offsets[1:] = torch.cumsum(sizes, 0, dtype=torch.int64)
+    host = offsets.cpu()
+    total = int(host[-1])
+    if not 1 <= total <= JPEG_MAX_COUNT:
+        raise OperandError(f"coef: the scans take {total} bytes; the output must stay below 2^31 (encode fewer frames per call)")
+    scan = torch.empty(total, dtype=torch.uint8, device=coef.device)
+    check(lib.vk_jpeg_entropy_write(_p(coef), _p(offsets), _p(scan), total, n, mcu_h, mcu_w, n * blocks, _stream()), "vk_jpeg_entropy_write")
+    return scan, host

@@ -5,7 +5,8 @@ Exported from vista_amd.sample_utils (where the reference's users look); `python
 Same names, arguments and defaults as the reference. Differences, all stated where they occur: the pictures are cropped, resized and normalised
 on the GPU (ops.load_img_batch, Pillow's LANCZOS byte for byte), frames are converted to 8 bit on the GPU (ops.frames_to_u8), nothing is
 shuffled between host and device (`--low_vram` is a no-op: 288 GB of HBM keep every stage resident), and without `imageio` a video is written as
-an animated PNG instead of an mp4.
+an animated PNG instead of an mp4 (or, with VISTA_VIDEO=mjpeg, as Motion-JPEG in AVI whose frames are encoded on the GPU: video_format, README
+"Videos").
 """
 import json
 import math
@@ -53,6 +54,27 @@ def sampler_name(sampler=None):
         where = " (environment hook VISTA_SAMPLER)" if sampler is None else ""
         raise ValueError(f"Unknown sampler {name}{where}: one of {', '.join(SAMPLERS)}")
     return name
+
+
+VIDEO_FORMATS = ("apng", "mjpeg")
+
+
+def video_format():
+    """-> (format, quality): how the front doors write videos. The one place the environment hooks VISTA_VIDEO and VISTA_VIDEO_QUALITY are read.
+    VISTA_VIDEO unset or `apng`: an mp4 through imageio where it is importable, else an animated PNG -- what was written before the hook existed,
+    byte for byte. `mjpeg`: `<stem>.avi`, Motion-JPEG frames encoded on the GPU (video.py) at VISTA_VIDEO_QUALITY (1 .. 100, default 90).
+    An unknown format or a bad quality is refused here, by name, before a model is built."""
+    name = os.environ.get("VISTA_VIDEO") or "apng"
+    if name not in VIDEO_FORMATS:
+        raise ValueError(f"Unknown video format {name} (environment hook VISTA_VIDEO): one of {', '.join(VIDEO_FORMATS)}")
+    text = os.environ.get("VISTA_VIDEO_QUALITY") or "90"
+    try:
+        quality = int(text)
+    except ValueError:
+        quality = 0
+    if not 1 <= quality <= 100:
+        raise ValueError(f"Bad JPEG quality {text} (environment hook VISTA_VIDEO_QUALITY): a whole number from 1 to 100")
+    return name, quality
 
 
 def get_sampler(sampler, steps, discretization_config, guider_config):
@@ -268,7 +290,15 @@ def _to_u8(samples, real, grid=False):
 
 def save_video(path_stem, frames_u8, fps=10):
     """(t, H, W, 3) uint8 -> `<stem>.mp4` through imageio where it is importable (the reference's writer); otherwise `<stem>.apng`, an animated
-    PNG at 1000 / fps ms per frame (lossless, so the frames read back exactly). Returns the path written."""
+    PNG at 1000 / fps ms per frame (lossless, so the frames read back exactly). With VISTA_VIDEO=mjpeg (video_format): `<stem>.avi`, Motion-JPEG;
+    the frames may then be a uint8 GPU tensor, which is encoded where it lies, or numpy, which is uploaded. Returns the path written."""
+    fmt, quality = video_format()
+    if fmt == "mjpeg":
+        from . import video
+        H, W = int(frames_u8.shape[1]), int(frames_u8.shape[2])
+        return video.write_avi(path_stem + ".avi", video.encode_jpeg(frames_u8, quality), W, H, fps)
+    if torch.is_tensor(frames_u8):
+        frames_u8 = frames_u8.cpu().numpy()
     try:
         import imageio
     except ImportError:
@@ -291,9 +321,17 @@ def save_video(path_stem, frames_u8, fps=10):
 
 
 def read_video_frames(path):
-    """The frames of an `.apng` written by save_video -> (t, H, W, 3) uint8."""
+    """The frames of an `.apng` or an `.avi` (Motion-JPEG, every chunk decoded by Pillow) written by save_video -> (t, H, W, 3) uint8."""
     import numpy as np
     from PIL import Image, ImageSequence
+    if path.lower().endswith(".avi"):
+        import io
+        from . import video
+        frames = []
+        for j in video.read_avi(path):
+            with Image.open(io.BytesIO(j)) as im:
+                frames.append(np.array(im.convert("RGB"), dtype=np.uint8))
+        return np.stack(frames)
     with Image.open(path) as im:
         return np.stack([np.array(frame.convert("RGB"), dtype=np.uint8) for frame in ImageSequence.Iterator(im)])
 
@@ -302,7 +340,8 @@ def perform_save_locally(save_path, samples, mode, dataset_name, sample_index):
     """Writes `samples` (n, 3, H, W) under save_path/mode with the reference's file names: images `<dataset>_<index:06>_<frame:04>.png`, grids
     `<dataset>_<index:06>.png`, videos `<dataset>_<index:06>.mp4` at 10 fps. A save_path containing "real" holds inputs in [-1, 1], any other
     samples in [0, 1]. The 8-bit conversion (and the make_grid layout) runs in vk_frames_to_u8. Deviation: without imageio the video is an
-    animated PNG (`.apng`, 100 ms per frame) instead of an mp4."""
+    animated PNG (`.apng`, 100 ms per frame) instead of an mp4; with VISTA_VIDEO=mjpeg it is `<stem>.avi` (README "Videos"), and the 8-bit frames
+    go from vk_frames_to_u8 to the JPEG kernels without leaving the GPU."""
     from PIL import Image
     if mode not in ("images", "grids", "videos"):
         raise AssertionError(mode)
@@ -315,5 +354,7 @@ def perform_save_locally(save_path, samples, mode, dataset_name, sample_index):
             Image.fromarray(frame).save(f"{stem}_{count:04}.png")
     elif mode == "grids":
         Image.fromarray(_to_u8(samples, real, grid=True)).save(stem + ".png")
+    elif video_format()[0] == "mjpeg":
+        save_video(stem, ops.frames_to_u8(samples.float(), real=real), 10)
     else:
         save_video(stem, _to_u8(samples, real), 10)

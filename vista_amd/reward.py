@@ -177,7 +177,7 @@ def save_heat_videos(save_dir, inputs, candidates, reports, dataset, sample_inde
     for name, fmap in zip(ran, maps):
         if tuple(inputs.shape[-2:]) != (HEAT_CELL * fmap.shape[-2], HEAT_CELL * fmap.shape[-1]):
             raise ValueError(f"save_heat_videos: a {tuple(fmap.shape[-2:])} map does not belong to {tuple(inputs.shape[-2:])} frames")
-        frames = ops.heat_overlay_u8(inputs.float(), fmap, vmax, alpha=HEAT_ALPHA).cpu().numpy()
+        frames = ops.heat_overlay_u8(inputs.float(), fmap, vmax, alpha=HEAT_ALPHA)   # (stays on the GPU: save_video moves it only for the PNG path)
         folder = os.path.join(save_dir, "heat", name, "videos")
         os.makedirs(folder, exist_ok=True)
         paths.append(SU.save_video(os.path.join(folder, f"{dataset}_{sample_index:06}"), frames, 10))
@@ -214,6 +214,7 @@ def main(argv=None):
     net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
     SU.check_sizes(opt.height, opt.width, opt.n_frames, 1, opt.n_conds, net_params)
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
+    SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
     if opt.ens_size < 2:
         raise ValueError(f"--ens_size {opt.ens_size}: reward estimation needs at least two ensemble members (unbiased variance)")
     if opt.heat_max is not None and not opt.heat_max > 0.0:
