@@ -259,15 +259,15 @@ def _fake_report(denoise_loss, scale, n_sigmas=2, T=3):
 
 @pytest.mark.parametrize("n_sigmas", [2, 1])
 def test_record_and_summary_formats(tmp_path, n_sigmas):
-    from vista_amd import denoise_loss
+    from vista_amd import denoise_loss, frontdoor
     opt = denoise_loss.parse_args().parse_args(["--rand_gen", "--n_sigmas", str(n_sigmas), "--n_frames", "3"])
     save = str(tmp_path / "out")
-    path = denoise_loss.start_records(save)
+    path = frontdoor.start_records(save, denoise_loss.RECORDS_NAME)
     records = []
     for index, scale in ((0, 1.0), (4, 3.0)):
         rec = denoise_loss.make_record(index, [f"scene{index}/a.png", "b.png", "c.png"], _fake_report(denoise_loss, scale, n_sigmas), opt,
                                        {"load": 0.12345678, "forward": 1.0})
-        assert denoise_loss.append_record(save, rec) == path
+        assert frontdoor.append_record(save, denoise_loss.RECORDS_NAME, rec) == path
         records.append(rec)
     with open(path) as f:
         lines = [json.loads(line) for line in f]
@@ -279,17 +279,17 @@ def test_record_and_summary_formats(tmp_path, n_sigmas):
     assert r["sigmas"] == denoise_loss.sigma_grid(n_sigmas) and len(r["loss"]) == n_sigmas and len(r["frame_mse"]) == n_sigmas
     assert all(len(row) == 3 for row in r["frame_mse"]) and r["timings"] == {"load": 0.1235, "forward": 1.0}
     assert r["settings"]["weighting"] == "V" and r["settings"]["additional_loss"] is True and r["settings"]["n_sigmas"] == n_sigmas
-    summary_path = denoise_loss.write_summary(save, records)
+    summary_path = frontdoor.write_summary(save, denoise_loss.SUMMARY_NAME, denoise_loss.summarize(records))
     with open(summary_path) as f:
         summary = json.load(f)
     assert os.path.basename(summary_path) == "loss_summary.json" and summary["scenes"] == 2 and summary["sigmas"] == r["sigmas"]
     assert summary["loss"] == [2.0 * (i + 1) for i in range(n_sigmas)] and summary["mse"] == [1.0] * n_sigmas
     assert summary["frame_mse"] == [[0.0, 2.0, 4.0]] * n_sigmas and summary["cond"] == [0]
-    denoise_loss.start_records(save)
+    frontdoor.start_records(save, denoise_loss.RECORDS_NAME)
     assert open(path).read() == "", "the file describes one run"
     bad = _fake_report(denoise_loss, float("nan"), n_sigmas)
     with pytest.raises(ValueError):
-        denoise_loss.append_record(save, denoise_loss.make_record(0, ["a"], bad, opt))
+        frontdoor.append_record(save, denoise_loss.RECORDS_NAME, denoise_loss.make_record(0, ["a"], bad, opt))
 
 
 def test_library_exports_the_loss_entry_points_and_the_plane_rule():

@@ -104,7 +104,7 @@ def _report(psnr, ssim):
 
 
 def test_records_and_summary_from_hand_made_reports(tmp_path):
-    from vista_amd import evaluate
+    from vista_amd import evaluate, frontdoor
     a = evaluate.make_record(4, ["a0.png", "a1.png"], _report([40.0, 30.0, 20.0, 10.0, 12.0, 8.0, 6.0], [0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.3]),
                              seed=23, action="traj", n_conds=1, n_rounds=2, n_frames=5, timings={"metrics": 0.123456})
     assert sorted(a) == sorted(["index", "frames", "seed", "action", "n_conds", "n_rounds", "frames_scored", "psnr", "ssim", "sse", "cond",
@@ -123,12 +123,12 @@ def test_records_and_summary_from_hand_made_reports(tmp_path):
     assert c["cond"] == [0, 1] and c["mean_psnr"] is None and c["mean_ssim"] is None and c["rounds"] == []
 
     save = str(tmp_path / "out")
-    assert evaluate.start_records(save) == os.path.join(save, "metrics.jsonl")
+    assert frontdoor.start_records(save, evaluate.RECORDS_NAME) == os.path.join(save, "metrics.jsonl")
     for rec in (a, b):
-        evaluate.append_record(save, rec)
+        frontdoor.append_record(save, evaluate.RECORDS_NAME, rec)
     lines = open(os.path.join(save, "metrics.jsonl")).read().splitlines()
     assert [json.loads(line) for line in lines] == [json.loads(json.dumps(a)), json.loads(json.dumps(b))] and "Infinity" not in "".join(lines)
-    evaluate.start_records(save)
+    frontdoor.start_records(save, evaluate.RECORDS_NAME)
     assert open(os.path.join(save, "metrics.jsonl")).read() == "", "a run starts its own file"
 
     s = evaluate.summarize([a, b, c])
@@ -138,7 +138,7 @@ def test_records_and_summary_from_hand_made_reports(tmp_path):
     assert s["horizon"]["ssim"] == [None, pytest.approx(0.9), pytest.approx(0.6), 0.6, 0.5, 0.4, 0.3]
     s2 = evaluate.summarize([a])
     assert s2["mean_psnr"] == a["mean_psnr"] and s2["horizon"]["psnr"][1:] == a["psnr"][1:] and s2["horizon"]["psnr"][0] is None
-    path = evaluate.write_summary(save, [a, b, c])
+    path = frontdoor.write_summary(save, evaluate.SUMMARY_NAME, evaluate.summarize([a, b, c]))
     assert path == os.path.join(save, "metrics_summary.json") and json.load(open(path)) == json.loads(json.dumps(s))
     assert evaluate.summarize([]) == {"scenes": 0, "mean_psnr": None, "mean_ssim": None, "horizon": {"frame": [], "scenes": [], "psnr": [], "ssim": []}}
 

@@ -234,14 +234,14 @@ def test_estimate_over_thread_ranks_equals_one_rank(kernels_in_torch):
 
 
 def test_record_writer_keeps_null_candidates(tmp_path):
-    from vista_amd import reward
+    from vista_amd import frontdoor, reward
     from vista_amd.reward_utils import RewardReport
     fv = torch.tensor([0.0, 0.25, 0.5], dtype=torch.float64)
     rep = RewardReport(reward=torch.tensor(math.exp(-0.25), dtype=torch.float64), mean_variance=0.25, frame_variance=fv, frame_reward=torch.exp(-fv))
     cands = [("traj", {"trajectory": torch.zeros(8)}, None), ("steer", None, "the scene's annotation has no speed / angle record")]
     record = reward.make_record(7, ["a/f0.jpg", "a/f1.jpg"], 23, 5, 10, cands, [rep], {"load": 0.5, "sample": 8.123456})
-    path = reward.append_record(str(tmp_path / "out"), record)
-    reward.append_record(str(tmp_path / "out"), record)
+    path = frontdoor.append_record(str(tmp_path / "out"), reward.RECORDS_NAME, record)
+    frontdoor.append_record(str(tmp_path / "out"), reward.RECORDS_NAME, record)
     lines = open(path).read().splitlines()
     assert path.endswith("rewards.jsonl") and len(lines) == 2 and lines[0] == lines[1]
     got = json.loads(lines[0])

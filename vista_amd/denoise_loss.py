@@ -23,18 +23,17 @@ replace_cond_frames. With --loss_type l1, e is the absolute error.
 Not built: several GPUs (WORLD_SIZE > 1) are refused by name; the natural multi-GPU form is scene i on rank i mod W with a merge of the records.
 The still IMG dataset is allowed: the loss of a still clip is well defined. Random conditioning-frame choices and gradients are not built.
 """
-import json
 import math
-import os
-import random
 import sys
 import time
 from statistics import NormalDist
 
-from . import config, sample
+from . import frontdoor, sample
+from .frontdoor import mean
 from . import sample_utils as SU
 
 WEIGHTINGS = {"V": "VWeighting", "EDM": "EDMWeighting", "Eps": "EpsWeighting", "Unit": "UnitWeighting"}
+RECORDS_NAME, SUMMARY_NAME = "loss.jsonl", "loss_summary.json"
 FIELDS = ("loss", "mse", "dynamics", "structure")
 
 
@@ -74,17 +73,7 @@ def check_run(opt, net_params=None):
         raise ValueError(f"--height {opt.height} --width {opt.width}: the structure term's Fourier high-pass keeps a latent plane in one workgroup's "
                          f"LDS, and a {opt.height // 8} x {opt.width // 8} plane does not fit (16 h w + 16 (h + w) <= 160 KiB; 72 x 128 does); "
                          "give --no_additional_loss for the plain denoising loss")
-    if opt.n_scenes < 0:
-        raise ValueError(f"--n_scenes {opt.n_scenes}: a count of scenes, or 0 for the whole dataset")
-    if opt.n_scenes == 0 and opt.rand_gen:
-        raise ValueError("--n_scenes 0 (to the end of the dataset) with the random walk: the reference's random walk never ends by itself; "
-                         "give --n_scenes N, or --rand_gen for the sequential walk")
-
-
-def check_world():
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError(f"WORLD_SIZE {os.environ['WORLD_SIZE']}: vista_amd.denoise_loss runs on one GPU (scene-per-rank scoring with a merge of "
-                         "the records is not built); start it without torch.distributed.run")
+    frontdoor.check_scene_count(opt)
 
 
 class LossReport:
@@ -132,14 +121,7 @@ def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames
         t0 = time.perf_counter()
         images = SU.load_img_seq(frame_list, height, width, "cuda")
         t0 = lap("load", t0)
-        unique_keys = set(e.input_key for e in model.conditioner.embedders)
-        value_dict = SU.init_embedder_options(unique_keys)
-        cond_img = images[:1]
-        value_dict["cond_frames_without_noise"] = cond_img
-        value_dict["cond_aug"] = cond_aug
-        value_dict["cond_frames"] = cond_img + cond_aug * torch.randn_like(cond_img)
-        for key, value in (action_dict or {}).items():
-            value_dict[key] = value
+        value_dict = frontdoor.first_window_values(model, images, cond_aug, action_dict)
         condition = getattr(model, "condition_fn", None) or SU.get_condition
         c, _uc = condition(model, value_dict, n_frames, sample.UC_KEYS, "cuda")   # (round 0's conditioning of sample.run; uc is dropped)
         t0 = lap("condition", t0)
@@ -183,16 +165,12 @@ def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames
 
 
 # ---- records ------------------------------------------------------------------------------------------------------------------------------
-def _mean(values):
-    return math.fsum(values) / len(values)
-
-
 def make_record(index, frame_list, report, opt_or_settings, timings=None):
     s = opt_or_settings if isinstance(opt_or_settings, dict) else settings_of(opt_or_settings)
     return {"index": int(index), "frames": [frame_list[0]], "seed": int(s["seed"]), "noise_seed": int(s["noise_seed"]), "settings": s,
             "sigmas": [float(v) for v in report.sigmas], **{k: [float(v) for v in getattr(report, k)] for k in FIELDS},
             "frame_mse": [[float(v) for v in row] for row in report.frame_mse], "cond": [int(i) for i in report.cond],
-            "timings": {k: round(float(v), 4) for k, v in (timings or {}).items()}}
+            "timings": frontdoor.rounded_timings(timings)}
 
 
 def settings_of(opt):
@@ -202,21 +180,6 @@ def settings_of(opt):
             "additional_loss_weight": opt.additional_loss_weight, "offset_noise_level": opt.offset_noise_level}
 
 
-def start_records(save_dir):
-    """An empty <save_dir>/loss.jsonl: the file describes one run, as the summary does. Returns its path."""
-    os.makedirs(save_dir, exist_ok=True)
-    path = os.path.join(save_dir, "loss.jsonl")
-    open(path, "w").close()
-    return path
-
-
-def append_record(save_dir, record):
-    path = os.path.join(save_dir, "loss.jsonl")
-    with open(path, "a") as f:
-        f.write(json.dumps(record, allow_nan=False) + "\n")
-    return path
-
-
 def summarize(records):
     """Scene count, the per-sigma means over scenes of every figure, and the per-frame curve (mean frame_mse over scenes, [n_sigmas][T])."""
     if not records:
@@ -224,70 +187,39 @@ def summarize(records):
     S = len(records[0]["sigmas"])
     T = len(records[0]["frame_mse"][0])
     return {"scenes": len(records), "sigmas": records[0]["sigmas"],
-            **{k: [_mean([r[k][i] for r in records]) for i in range(S)] for k in FIELDS},
-            "frame_mse": [[_mean([r["frame_mse"][i][t] for r in records]) for t in range(T)] for i in range(S)], "cond": records[0]["cond"]}
-
-
-def write_summary(save_dir, records):
-    os.makedirs(save_dir, exist_ok=True)
-    path = os.path.join(save_dir, "loss_summary.json")
-    with open(path, "w") as f:
-        json.dump(summarize(records), f, allow_nan=False, indent=1)
-        f.write("\n")
-    return path
+            **{k: [mean([r[k][i] for r in records]) for i in range(S)] for k in FIELDS},
+            "frame_mse": [[mean([r["frame_mse"][i][t] for r in records]) for t in range(T)] for i in range(S)], "cond": records[0]["cond"]}
 
 
 def _scene_line(record):
     return (f"denoise_loss {record['index']}: " + ", ".join(f"sigma {s:.3g} loss {v:.5g}" for s, v in zip(record["sigmas"], record["loss"])) + " | "
-            + ", ".join(f"{k} {v:.2f} s" for k, v in record["timings"].items()))
+            + frontdoor.timings_text(record["timings"]))
 
 
 def main(argv=None):
     opt, _unknown = parse_args(prog="python -m vista_amd.denoise_loss").parse_known_args(argv)
     # what cannot run is refused here, before 2.5 billion parameters are built
-    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
-    check_run(opt, net_params)
-    check_world()
+    check_run(opt, frontdoor.net_params(opt))
+    frontdoor.check_world("denoise_loss", "scene-per-rank scoring with a merge of the records is not built")
     return _loss_loop(opt)
 
 
 def _loss_loop(opt):
     """The walk of vista_amd.sample over the dataset with the loss behind every scene."""
-    if opt.low_vram:
-        print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
-    spec = dict(SU.VERSION2SPECS[opt.version])
-    if opt.config:
-        spec["config"] = opt.config
-    if opt.ckpt:
-        spec["ckpt"] = opt.ckpt
-    model = SU.init_model(spec)
-    start_records(opt.save)
+    model = frontdoor.build_model(opt)
+    frontdoor.start_records(opt.save, RECORDS_NAME)
     records, settings = [], settings_of(opt)
-
-    sample_index = 0
-    while sample_index >= 0:
-        sample.seed_everything(opt.seed)
-        frame_list, sample_index, dataset_length, action_dict = SU.get_sample(sample_index, opt.dataset, opt.n_frames, opt.action,
-                                                                              data_root=opt.data_root, anno_file=opt.anno_file)
+    for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt, n_scenes=opt.n_scenes):
         timings = {}
         report = run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames, n_conds=opt.n_conds,
                      cond_aug=opt.cond_aug, n_sigmas=opt.n_sigmas, p_mean=opt.p_mean, p_std=opt.p_std, loss_type=opt.loss_type,
                      weighting=opt.weighting, additional=not opt.no_additional_loss, additional_loss_weight=opt.additional_loss_weight,
                      offset_noise_level=opt.offset_noise_level, noise_seed=opt.noise_seed, timings=timings)
         record = make_record(sample_index, frame_list, report, settings, timings)
-        append_record(opt.save, record)
+        frontdoor.append_record(opt.save, RECORDS_NAME, record)
         records.append(record)
         print(_scene_line(record), flush=True)
-
-        if opt.n_scenes and len(records) >= opt.n_scenes:
-            break
-        if opt.rand_gen:
-            sample_index += random.randint(1, max(1, dataset_length - 1))
-        else:
-            sample_index += 1
-            if dataset_length <= sample_index:
-                sample_index = -1
-    write_summary(opt.save, records)
+    frontdoor.write_summary(opt.save, SUMMARY_NAME, summarize(records))
     return 0
 
 

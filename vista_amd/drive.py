@@ -36,15 +36,15 @@ import collections
 import json
 import math
 import os
-import random
 import sys
 import time
 
-from . import config, sample
+from . import frontdoor, sample
 from . import sample_utils as SU
 from .evaluate import frame_round   # (the round that produced frame i of a rollout)
 
 ACTION_LENGTHS = {"command": 1, "trajectory": 4, "speed": 4, "angle": 4, "goal": 2}   # trajectory: 4 (forward, left) pairs
+RECORDS_NAME = "drive.jsonl"
 RECORD_KEYS = ("index", "frames", "seed", "action", "n_rounds", "rounds", "timings")
 RoundResult = collections.namedtuple("RoundResult", "round lo hi latents action")
 
@@ -58,7 +58,7 @@ def round_range(r, n_frames):
 
 
 # ---- the script -----------------------------------------------------------------------------------------------------------------------------------
-def _number(v):
+def _is_finite_number(v):
     return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
 
 
@@ -75,11 +75,11 @@ def check_entry(entry, where="script entry"):
             if not isinstance(value, int) or isinstance(value, bool):
                 raise ValueError(f"{where}: command must be one integer, got {value!r}")
         elif key == "trajectory":
-            if not (isinstance(value, list) and len(value) == 4 and all(isinstance(p, list) and len(p) == 2 and all(_number(x) for x in p) for p in value)):
+            if not (isinstance(value, list) and len(value) == 4 and all(isinstance(p, list) and len(p) == 2 and all(_is_finite_number(x) for x in p) for p in value)):
                 raise ValueError(f"{where}: trajectory must be 4 [forward, left] pairs of numbers, got {value!r}")
         else:
             n = ACTION_LENGTHS[key]
-            if not (isinstance(value, list) and len(value) == n and all(_number(x) for x in value)):
+            if not (isinstance(value, list) and len(value) == n and all(_is_finite_number(x) for x in value)):
                 raise ValueError(f"{where}: {key} must be {n} numbers, got {value!r}")
             if key == "goal" and not (0 < value[0] < 1600 and 0 < value[1] < 900):
                 raise ValueError(f"{where}: goal {value!r} lies outside the open 1600 x 900 camera frame")
@@ -319,15 +319,7 @@ def parse_args(**parser_kwargs):
 
 def n_rounds_given(argv):
     """Whether the command line names --n_rounds (under any abbreviation argparse accepts), and its value."""
-    parser = parse_args()
-    parser.set_defaults(n_rounds=None)
-    return parser.parse_known_args(argv)[0].n_rounds
-
-
-def check_world():
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError(f"WORLD_SIZE {os.environ['WORLD_SIZE']}: vista_amd.drive runs on one GPU (a frame-sharded session is not built); start it "
-                         "without torch.distributed.run")
+    return frontdoor.n_rounds_given(parse_args, argv)
 
 
 def plan_run(opt, argv=None, net_params=None):
@@ -342,7 +334,7 @@ def plan_run(opt, argv=None, net_params=None):
         if opt.n_rounds < 1:
             raise ValueError(f"--n_rounds {opt.n_rounds}: a rollout has at least one round")
         entries = ["scene"] * opt.n_rounds
-    check_world()
+    frontdoor.check_world("drive", "a frame-sharded session is not built")
     SU.check_sizes(opt.height, opt.width, opt.n_frames, len(entries), opt.n_conds, net_params)
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
@@ -353,15 +345,14 @@ def make_record(index, frame_list, entries, *, seed, action, n_frames, timings=N
     """The JSON record of one scene; "action" of a round is the script's entry as given."""
     rounds = [{"round": r, "action": e, "frames": list(round_range(r, n_frames))} for r, e in enumerate(entries)]
     return {"index": int(index), "frames": [frame_list[0]], "seed": int(seed), "action": str(action), "n_rounds": len(entries), "rounds": rounds,
-            "timings": {k: round(float(v), 4) for k, v in (timings or {}).items()}}
+            "timings": frontdoor.rounded_timings(timings)}
 
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     opt, _unknown = parse_args(prog="python -m vista_amd.drive").parse_known_args(argv)
     # what cannot run is refused here, before 2.5 billion parameters are built
-    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
-    entries = plan_run(opt, argv, net_params)
+    entries = plan_run(opt, argv, frontdoor.net_params(opt))
     return _drive_loop(opt, entries)
 
 
@@ -372,34 +363,20 @@ def _step_entries(session, entries, scene_action, timings, where):
     return entries, None
 
 
-def _drive_loop(opt, entries, step_rounds=_step_entries, records_name="drive.jsonl", label="drive"):
+def _drive_loop(opt, entries, step_rounds=_step_entries, records_name=RECORDS_NAME, label="drive"):
     """The loop of vista_amd.sample with a DriveSession in place of do_sample. `step_rounds(session, entries, scene_action, timings, where)` steps
     the session len(entries) times and returns (the entry every round ran under, one dict per round to merge into the record's rounds, or
     None); vista_amd.plan passes its own, which scores a list of candidates before every step, and writes plan.jsonl."""
     import torch
     from . import ops
-    if opt.low_vram:
-        print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
-    spec = dict(SU.VERSION2SPECS[opt.version])
-    if opt.config:
-        spec["config"] = opt.config
-    if opt.ckpt:
-        spec["ckpt"] = opt.ckpt
-    model = SU.init_model(spec)
-    virtual_path, real_path = os.path.join(opt.save, "virtual"), os.path.join(opt.save, "real")
-    os.makedirs(opt.save, exist_ok=True)
-    records_path = os.path.join(opt.save, records_name)
-    open(records_path, "w").close()   # the file describes this run only
+    model = frontdoor.build_model(opt)
+    frontdoor.start_records(opt.save, records_name)   # the file describes this run only
 
     def clock():
         torch.cuda.synchronize()
         return time.perf_counter()
 
-    sample_index = 0
-    while sample_index >= 0:
-        sample.seed_everything(opt.seed)
-        frame_list, sample_index, dataset_length, scene_action = SU.get_sample(sample_index, opt.dataset, opt.n_frames, opt.action,
-                                                                               data_root=opt.data_root, anno_file=opt.anno_file)
+    for frame_list, sample_index, _dataset_length, scene_action in frontdoor.walk(opt):
         timings = {}
         t0 = clock()
         session = DriveSession(model, frame_list, height=opt.height, width=opt.width, n_frames=opt.n_frames, n_conds=opt.n_conds,
@@ -411,9 +388,7 @@ def _drive_loop(opt, entries, step_rounds=_step_entries, records_name="drive.jso
         samples, inputs = session.frames(), session.inputs
         t3 = clock()
         timings.update(load=t1 - t0, sample=t2 - t1 - timings.get("score", 0.0), decode=t3 - t2)
-        for path, frames in ((virtual_path, samples), (real_path, inputs)):
-            for mode in ("videos", "grids", "images"):
-                SU.perform_save_locally(path, frames, mode, opt.dataset, sample_index)
+        frontdoor.save_pictures(opt.save, opt.dataset, sample_index, virtual=samples, real=inputs)
         t4 = clock()
         timings["save"] = t4 - t3
         if opt.hud:
@@ -425,16 +400,8 @@ def _drive_loop(opt, entries, step_rounds=_step_entries, records_name="drive.jso
         record = make_record(sample_index, frame_list, stepped, seed=opt.seed, action=opt.action, n_frames=opt.n_frames, timings=timings)
         for round_record, extra in zip(record["rounds"], extras or ()):
             round_record.update(extra)
-        with open(records_path, "a") as f:
-            f.write(json.dumps(record, allow_nan=False) + "\n")
-        print(f"{label} {sample_index}: {len(entries)} rounds, " + ", ".join(f"{k} {v:.2f} s" for k, v in timings.items()), flush=True)
-
-        if opt.rand_gen:
-            sample_index += random.randint(1, max(1, dataset_length - 1))
-        else:
-            sample_index += 1
-            if dataset_length <= sample_index:
-                sample_index = -1
+        frontdoor.append_record(opt.save, records_name, record)
+        print(f"{label} {sample_index}: {len(entries)} rounds, " + frontdoor.timings_text(timings), flush=True)
     return 0
 
 

@@ -18,18 +18,18 @@ Not built: the IMG dataset (one picture repeated has no future to compare agains
 natural multi-GPU form is scene i on rank i mod W with a merge of the records. Perceptual metrics that need a pretrained network are not built.
 """
 import json
-import math
 import os
-import random
 import re
 import sys
 import time
 
-from . import config, fidelity, sample
+from . import fidelity, frontdoor, sample
+from .frontdoor import json_number, mean
 from ._lib import VistaHipError
 from . import sample_utils as SU
 
 PICTURE_NAME = re.compile(r"^(?P<dataset>.+)_(?P<index>\d{6})_(?P<frame>\d{4})\.png$")   # perform_save_locally's image names
+RECORDS_NAME, SUMMARY_NAME = "metrics.jsonl", "metrics_summary.json"
 
 
 def parse_args(**parser_kwargs):
@@ -52,17 +52,11 @@ def check_run(opt, net_params=None):
     if opt.dataset == "IMG":
         raise ValueError("--dataset IMG: one picture repeated has no future frames to score a prediction against; evaluate needs a dataset "
                          "of annotated scenes (NUSCENES)")
-    if opt.n_scenes < 0:
-        raise ValueError(f"--n_scenes {opt.n_scenes}: a count of scenes, or 0 for the whole dataset")
-    if opt.n_scenes == 0 and opt.rand_gen:
-        raise ValueError("--n_scenes 0 (to the end of the dataset) with the random walk: the reference's random walk never ends by itself; "
-                         "give --n_scenes N, or --rand_gen for the sequential walk")
+    frontdoor.check_scene_count(opt)
 
 
 def check_world():
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError(f"WORLD_SIZE {os.environ['WORLD_SIZE']}: vista_amd.evaluate runs on one GPU (scene-per-rank evaluation with a merge of "
-                         "the records is not built); start it without torch.distributed.run")
+    frontdoor.check_world("evaluate", "scene-per-rank evaluation with a merge of the records is not built")
 
 
 def rollout_length(n_frames, n_rounds):
@@ -87,17 +81,6 @@ def future_frames(index, n_frames, upto, dataset="NUSCENES", data_root=None, ann
 
 
 # ---- records ------------------------------------------------------------------------------------------------------------------------------
-def _num(v):
-    """A float for JSON: None where it is not finite (an infinite PSNR, a mean over nothing)."""
-    v = float(v)
-    return v if math.isfinite(v) else None
-
-
-def _mean(values):
-    """The mean of a list of floats in float64, in list order; nan for an empty list."""
-    return math.fsum(values) / len(values) if values else float("nan")
-
-
 def frame_round(i, n_frames):
     """The sampling round that produced frame i of a rollout: the first window holds n_frames, every later one adds n_frames - 3."""
     return 0 if i < n_frames else 1 + (i - n_frames) // (n_frames - 3)
@@ -113,30 +96,13 @@ def make_record(index, frame_list, report, *, seed, action, n_conds, n_rounds, n
     for r in range(max(1, n_rounds)):
         members = [i for i in pred if frame_round(i, n_frames) == r]
         if members:
-            rounds.append({"round": r, "frames": len(members), "mean_psnr": _num(_mean([psnr[i] for i in members])),
-                           "mean_ssim": _num(_mean([ssim[i] for i in members]))})
+            rounds.append({"round": r, "frames": len(members), "mean_psnr": json_number(mean([psnr[i] for i in members])),
+                           "mean_ssim": json_number(mean([ssim[i] for i in members]))})
     return {"index": int(index), "frames": [frame_list[0]], "seed": int(seed), "action": str(action), "n_conds": int(n_conds),
             "n_rounds": int(n_rounds), "frames_scored": scored,
-            "psnr": [_num(v) for v in psnr], "ssim": [_num(v) for v in ssim], "sse": [[int(c) for c in row] for row in report.sse],
-            "cond": cond, "mean_psnr": _num(_mean([psnr[i] for i in pred])), "mean_ssim": _num(_mean([ssim[i] for i in pred])),
-            "rounds": rounds, "timings": {k: round(float(v), 4) for k, v in (timings or {}).items()}}
-
-
-def start_records(save_dir):
-    """An empty <save_dir>/metrics.jsonl: the file describes one run, as the summary does. Returns its path."""
-    os.makedirs(save_dir, exist_ok=True)
-    path = os.path.join(save_dir, "metrics.jsonl")
-    open(path, "w").close()
-    return path
-
-
-def append_record(save_dir, record):
-    """One line per scene at the end of <save_dir>/metrics.jsonl. Returns the file's path."""
-    os.makedirs(save_dir, exist_ok=True)
-    path = os.path.join(save_dir, "metrics.jsonl")
-    with open(path, "a") as f:
-        f.write(json.dumps(record, allow_nan=False) + "\n")
-    return path
+            "psnr": [json_number(v) for v in psnr], "ssim": [json_number(v) for v in ssim], "sse": [[int(c) for c in row] for row in report.sse],
+            "cond": cond, "mean_psnr": json_number(mean([psnr[i] for i in pred])), "mean_ssim": json_number(mean([ssim[i] for i in pred])),
+            "rounds": rounds, "timings": frontdoor.rounded_timings(timings)}
 
 
 def summarize(records):
@@ -144,7 +110,7 @@ def summarize(records):
     (not a conditioning) frame. null where no scene did, or where a PSNR in the mean is infinite (written as null in the record)."""
     def scene_mean(key):
         vals = [r[key] for r in records if r["frames_scored"] > len(r["cond"])]
-        return None if not vals or any(v is None for v in vals) else _num(_mean(vals))
+        return None if not vals or any(v is None for v in vals) else json_number(mean(vals))
     length = max((r["frames_scored"] for r in records), default=0)
     horizon = {"frame": list(range(length)), "scenes": [], "psnr": [], "ssim": []}
     for i in range(length):
@@ -152,17 +118,8 @@ def summarize(records):
         horizon["scenes"].append(len(has))
         for key in ("psnr", "ssim"):
             vals = [r[key][i] for r in has]
-            horizon[key].append(None if not vals or any(v is None for v in vals) else _num(_mean(vals)))
+            horizon[key].append(None if not vals or any(v is None for v in vals) else json_number(mean(vals)))
     return {"scenes": len(records), "mean_psnr": scene_mean("mean_psnr"), "mean_ssim": scene_mean("mean_ssim"), "horizon": horizon}
-
-
-def write_summary(save_dir, records):
-    os.makedirs(save_dir, exist_ok=True)
-    path = os.path.join(save_dir, "metrics_summary.json")
-    with open(path, "w") as f:
-        json.dump(summarize(records), f, allow_nan=False, indent=1)
-        f.write("\n")
-    return path
 
 
 # ---- offline: the pictures of an earlier run ----------------------------------------------------------------------------------------------------
@@ -195,7 +152,7 @@ def compare(opt):
     scenes = picture_pairs(opt.compare)
     if not torch.cuda.is_available():
         raise VistaHipError("evaluate --compare: no GPU is visible; vista_amd runs on the MI355X only (no CPU / eager fallback)")
-    start_records(opt.compare)
+    frontdoor.start_records(opt.compare, RECORDS_NAME)
     records = []
     for dataset, index, frames in scenes:
         t0 = time.perf_counter()
@@ -213,17 +170,17 @@ def compare(opt):
         timings = {"load": t1 - t0, "metrics": time.perf_counter() - t1}
         record = make_record(index, [frames[0][2]], report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
                              n_frames=opt.n_frames, timings=timings)
-        append_record(opt.compare, record)
+        frontdoor.append_record(opt.compare, RECORDS_NAME, record)
         records.append(record)
         print(_scene_line(record), flush=True)
-    write_summary(opt.compare, records)
+    frontdoor.write_summary(opt.compare, SUMMARY_NAME, summarize(records))
     return 0
 
 
 def _scene_line(record):
     shown = ", ".join(f"{k} " + ("null" if record[k] is None else f"{record[k]:.4f}") for k in ("mean_psnr", "mean_ssim"))
     return (f"evaluate {record['index']}: {record['frames_scored']} frames, {shown} | "
-            + ", ".join(f"{k} {v:.2f} s" for k, v in record["timings"].items()))
+            + frontdoor.timings_text(record["timings"]))
 
 
 # ---- online ---------------------------------------------------------------------------------------------------------------------------------
@@ -232,8 +189,7 @@ def main(argv=None):
     if opt.compare is not None:
         return compare(opt)
     # what cannot run is refused here, before 2.5 billion parameters are built
-    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
-    check_run(opt, net_params)
+    check_run(opt, frontdoor.net_params(opt))
     check_world()
     return _evaluate_loop(opt)
 
@@ -241,23 +197,10 @@ def main(argv=None):
 def _evaluate_loop(opt):
     """The loop of vista_amd.sample with the metrics stage behind every scene."""
     import torch
-    if opt.low_vram:
-        print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
-    spec = dict(SU.VERSION2SPECS[opt.version])
-    if opt.config:
-        spec["config"] = opt.config
-    if opt.ckpt:
-        spec["ckpt"] = opt.ckpt
-    model = SU.init_model(spec)
-    virtual_path, real_path = os.path.join(opt.save, "virtual"), os.path.join(opt.save, "real")
-    start_records(opt.save)
+    model = frontdoor.build_model(opt)
+    frontdoor.start_records(opt.save, RECORDS_NAME)
     records = []
-
-    sample_index = 0
-    while sample_index >= 0:
-        sample.seed_everything(opt.seed)
-        frame_list, sample_index, dataset_length, action_dict = SU.get_sample(sample_index, opt.dataset, opt.n_frames, opt.action,
-                                                                              data_root=opt.data_root, anno_file=opt.anno_file)
+    for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt, n_scenes=opt.n_scenes):
         timings = {}
         samples, _samples_z, inputs = sample.run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames,
                                                  n_rounds=opt.n_rounds, n_conds=opt.n_conds, n_steps=opt.n_steps, cfg_scale=opt.cfg_scale,
@@ -277,25 +220,14 @@ def _evaluate_loop(opt):
         timings["metrics"] = time.perf_counter() - t0
         if not opt.no_pictures:
             t0 = time.perf_counter()
-            for path, frames in ((virtual_path, samples), (real_path, real)):
-                for mode in ("videos", "grids", "images"):
-                    SU.perform_save_locally(path, frames, mode, opt.dataset, sample_index)
+            frontdoor.save_pictures(opt.save, opt.dataset, sample_index, virtual=samples, real=real)
             timings["save"] = time.perf_counter() - t0
         record = make_record(sample_index, frame_list, report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
                              n_frames=opt.n_frames, timings=timings)
-        append_record(opt.save, record)
+        frontdoor.append_record(opt.save, RECORDS_NAME, record)
         records.append(record)
         print(_scene_line(record), flush=True)
-
-        if opt.n_scenes and len(records) >= opt.n_scenes:
-            break
-        if opt.rand_gen:
-            sample_index += random.randint(1, max(1, dataset_length - 1))
-        else:
-            sample_index += 1
-            if dataset_length <= sample_index:
-                sample_index = -1
-    write_summary(opt.save, records)
+    frontdoor.write_summary(opt.save, SUMMARY_NAME, summarize(records))
     return 0
 
 

@@ -39,18 +39,18 @@ search deeper than one round.
 import collections
 import functools
 import json
-import math
-import os
 import sys
 import time
 
-from . import config, drive, sample
+from . import drive, frontdoor, sample
+from .frontdoor import json_number
 from . import sample_utils as SU
 
 CandidateScores = collections.namedtuple("CandidateScores", "best reward mean_variance frame_variance t0 map")
 CandidateScores.__doc__ = """What one round's candidates scored. best: the index of the highest reward (the smallest variance total: ties to the
 lowest index, a NaN never), -1 if every candidate's total is NaN; reward (K,), mean_variance (K,), frame_variance (K, T') float64 on the CPU;
 t0: the first scored frame of the window (T' = T - t0); map (K, T', h, w) float32 on the GPU, or None."""
+RECORDS_NAME = "plan.jsonl"
 ENS_MAX = 64   # vk_candidate_frame_stats takes 2 .. 64 members
 
 
@@ -182,15 +182,7 @@ def parse_args(**parser_kwargs):
 
 def n_rounds_given(argv):
     """Whether the command line names --n_rounds (under any abbreviation argparse accepts), and its value."""
-    parser = parse_args()
-    parser.set_defaults(n_rounds=None)
-    return parser.parse_known_args(argv)[0].n_rounds
-
-
-def check_world():
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError(f"WORLD_SIZE {os.environ['WORLD_SIZE']}: vista_amd.plan runs on one GPU (neither a frame-sharded session nor members "
-                         "over ranks are built); start it without torch.distributed.run")
+    return frontdoor.n_rounds_given(parse_args, argv)
 
 
 def plan_run(opt, argv=None, net_params=None):
@@ -212,7 +204,7 @@ def plan_run(opt, argv=None, net_params=None):
         check_ensemble(opt.ens_size, opt.score_steps)
     except ValueError as e:
         raise ValueError("--" + str(e)) from None
-    check_world()
+    frontdoor.check_world("plan", "neither a frame-sharded session nor members over ranks are built")
     SU.check_sizes(opt.height, opt.width, opt.n_frames, len(rounds), opt.n_conds, net_params)
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
@@ -228,11 +220,6 @@ def unsupplied(action_mode, scene_action):
     return _WHY_EMPTY.get(action_mode, "the scene's annotation does not supply this action")
 
 
-def _number(v):
-    v = float(v)
-    return v if math.isfinite(v) else None   # (the record is strict JSON: a candidate whose ensemble went non-finite reports null)
-
-
 def round_extra(entries, live, scores, reason):
     """What a round adds to its record: `entries` the round's candidates as given, `live` the indices of those that were scored (in score
     order), `reason` why the others ("scene" entries the annotation cannot supply) were not."""
@@ -243,8 +230,9 @@ def round_extra(entries, live, scores, reason):
             candidates.append({"action": entry, "reward": None, "reason": reason})
             continue
         i = row[k]
-        candidates.append({"action": entry, "reward": _number(scores.reward[i]), "mean_variance": _number(scores.mean_variance[i]),
-                           "frame_variance": [_number(v) for v in scores.frame_variance[i]]})
+        # (the record is strict JSON: a candidate whose ensemble went non-finite reports null)
+        candidates.append({"action": entry, "reward": json_number(scores.reward[i]), "mean_variance": json_number(scores.mean_variance[i]),
+                           "frame_variance": [json_number(v) for v in scores.frame_variance[i]]})
     return {"candidates": candidates, "chosen": live[scores.best]}
 
 
@@ -276,9 +264,8 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     opt, _unknown = parse_args(prog="python -m vista_amd.plan").parse_known_args(argv)
     # what cannot run is refused here, before 2.5 billion parameters are built
-    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
-    rounds = plan_run(opt, argv, net_params)
-    return drive._drive_loop(opt, rounds, step_rounds=functools.partial(plan_rounds, opt), records_name="plan.jsonl", label="plan")
+    rounds = plan_run(opt, argv, frontdoor.net_params(opt))
+    return drive._drive_loop(opt, rounds, step_rounds=functools.partial(plan_rounds, opt), records_name=RECORDS_NAME, label="plan")
 
 
 if __name__ == "__main__":

@@ -17,21 +17,20 @@ all_reduce per candidate completes the ensemble on every rank, and rank 0 writes
 `run(...)` is the loop body as a function (returns the reports instead of writing files), `main(argv)` the loop of reward.py:212-266.
 """
 import contextlib
-import json
 import os
-import random
 import sys
 import time
 
 import torch
 
-from . import config, ops, reward_utils
+from . import frontdoor, ops, reward_utils
 from . import sample_utils as SU
-from .sample import UC_KEYS, _StageClock, seed_everything
+from .sample import UC_KEYS, _StageClock, seed_everything   # noqa: F401  (seed_everything: for the callers of run)
 
 ACTION_MODES = ("free", "traj", "trajectory", "cmd", "command", "steer", "goal")
 HEAT_CELL = 8       # the first stage maps 8 x 8 pixels to one latent pixel
 HEAT_ALPHA = 0.6
+RECORDS_NAME = "rewards.jsonl"
 _WHY_EMPTY = {"steer": "the scene's annotation has no speed / angle record", "goal": "the scene's goal point does not project into the camera frame"}
 
 
@@ -109,12 +108,7 @@ def run(model, frame_list, action_dicts, *, height=576, width=1024, n_frames=25,
     images = SU.load_img_seq(frame_list, height, width, "cuda")
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    unique_keys = set(e.input_key for e in model.conditioner.embedders)
-    base = SU.init_embedder_options(unique_keys)
-    cond_img = images[:1]
-    base["cond_frames_without_noise"] = cond_img
-    base["cond_aug"] = cond_aug
-    base["cond_frames"] = cond_img + cond_aug * torch.randn_like(cond_img)
+    base = frontdoor.first_window_values(model, images, cond_aug)
     value_dicts = []
     for action in action_dicts:
         value_dict = dict(base)
@@ -150,17 +144,7 @@ def make_record(index, frame_list, seed, ens_size, n_steps, candidates, reports,
         actions.append({"action": name, "reward": float(rep.reward), "mean_variance": float(rep.mean_variance),
                         "frame_variance": [float(v) for v in rep.frame_variance]})
     return {"index": int(index), "frames": [frame_list[0]], "seed": int(seed), "ens_size": int(ens_size), "n_steps": int(n_steps),
-            "actions": actions, "timings": {k: round(float(v), 4) for k, v in (timings or {}).items()}}
-
-
-def append_record(save_dir, record):
-    """One line per scene at the end of <save_dir>/rewards.jsonl. Returns the file's path."""
-    os.makedirs(save_dir, exist_ok=True)
-    path = os.path.join(save_dir, "rewards.jsonl")
-    line = json.dumps(record, allow_nan=False)
-    with open(path, "a") as f:
-        f.write(line + "\n")
-    return path
+            "actions": actions, "timings": frontdoor.rounded_timings(timings)}
 
 
 def save_heat_videos(save_dir, inputs, candidates, reports, dataset, sample_index, heat_max=None):
@@ -190,16 +174,8 @@ def init_distributed(ens_size):
     whole on its rank. -> (global rank, world, communicator). The caller owns the process group (destroy_process_group)."""
     import torch.distributed as dist
     from .parallel import DistComm
-    world, rank = int(os.environ["WORLD_SIZE"]), int(os.environ.get("RANK", "0"))
-    reward_utils.member_slots(ens_size, world)   # refuses world > ens_size by name, before anything is joined
-    backend = os.environ.get("VISTA_DIST_BACKEND", "nccl")
-    dev = int(os.environ.get("VISTA_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    torch.cuda.set_device(dev)
-    if backend == "nccl":
-        dist.init_process_group("nccl", device_id=torch.device("cuda", dev))   # "nccl" is RCCL on ROCm
-    else:
-        dist.init_process_group(backend)
+    reward_utils.member_slots(ens_size, int(os.environ["WORLD_SIZE"]))   # refuses world > ens_size by name, before anything is joined
+    rank, world, _dev = frontdoor.join_process_group()
     try:
         comm = DistComm(None, name="ensemble")
     except BaseException:
@@ -211,8 +187,7 @@ def init_distributed(ens_size):
 def main(argv=None):
     opt, _unknown = parse_args(prog="python -m vista_amd.reward").parse_known_args(argv)
     # what cannot run is refused here, before 2.5 billion parameters are built
-    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
-    SU.check_sizes(opt.height, opt.width, opt.n_frames, 1, opt.n_conds, net_params)
+    SU.check_sizes(opt.height, opt.width, opt.n_frames, 1, opt.n_conds, frontdoor.net_params(opt))
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
     if opt.ens_size < 2:
@@ -232,21 +207,11 @@ def main(argv=None):
 
 def _reward_loop(opt, names, rank, members, comm):
     """The loop of reward.py:212-266. Every rank of a job walks the same sample indices (the walk is a function of the seed); rank 0 writes."""
-    if opt.low_vram and rank == 0:
-        print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
-    spec = dict(SU.VERSION2SPECS[opt.version])
-    if opt.config:
-        spec["config"] = opt.config
-    if opt.ckpt:
-        spec["ckpt"] = opt.ckpt
-    model = SU.init_model(spec)
-    real_path = os.path.join(opt.save, "real")
+    model = frontdoor.build_model(opt, rank)
 
-    sample_index = 0
-    while sample_index >= 0:
-        seed_everything(opt.seed)
-        frame_list, sample_index, dataset_length, candidates = scene_candidates(sample_index, opt.dataset, opt.n_frames, names,
-                                                                                data_root=opt.data_root, anno_file=opt.anno_file)
+    def get_scene(index, dataset, n_frames, _action, **where):   # (the candidates of --action in place of its one action)
+        return scene_candidates(index, dataset, n_frames, names, **where)
+    for frame_list, sample_index, _dataset_length, candidates in frontdoor.walk(opt, get_scene):
         timings, inputs = {}, []
         action_dicts = [action for _, action, _ in candidates if action is not None]
         reports = []
@@ -257,22 +222,14 @@ def _reward_loop(opt, names, rank, members, comm):
         if rank == 0:
             t0 = time.perf_counter()
             images = inputs[0] if inputs else SU.load_img_seq(frame_list, opt.height, opt.width, "cuda")
-            for mode in ("videos", "grids", "images"):
-                SU.perform_save_locally(real_path, images, mode, opt.dataset, sample_index)
+            frontdoor.save_pictures(opt.save, opt.dataset, sample_index, real=images)
             if opt.save_maps and reports:
                 save_heat_videos(opt.save, images, candidates, reports, opt.dataset, sample_index, opt.heat_max)
             timings["save"] = time.perf_counter() - t0
             record = make_record(sample_index, frame_list, opt.seed, opt.ens_size, opt.n_steps, candidates, reports, timings)
-            append_record(opt.save, record)
+            frontdoor.append_record(opt.save, RECORDS_NAME, record)
             shown = ", ".join(f"{a['action']} " + ("null" if a["reward"] is None else f"{a['reward']:.6f}") for a in record["actions"])
-            print(f"reward {sample_index}: {shown} | " + ", ".join(f"{k} {v:.2f} s" for k, v in timings.items()), flush=True)
-
-        if opt.rand_gen:
-            sample_index += random.randint(1, max(1, dataset_length - 1))
-        else:
-            sample_index += 1
-            if dataset_length <= sample_index:
-                sample_index = -1
+            print(f"reward {sample_index}: {shown} | " + frontdoor.timings_text(timings), flush=True)
     return 0
 
 

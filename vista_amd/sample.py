@@ -16,14 +16,14 @@ rank 0 writes the files.
 """
 import argparse
 import os
-import random
 import sys
 import time
 
 import torch
 
-from . import config
+from . import frontdoor
 from . import sample_utils as SU
+from .frontdoor import seed_everything   # noqa: F401  (where the reference's users, and the other front doors, look for it)
 
 UC_KEYS = ["cond_frames", "cond_frames_without_noise", "command", "trajectory", "speed", "angle", "goal"]
 
@@ -53,16 +53,6 @@ def parse_args(**parser_kwargs):
     add("--anno_file", type=str, default=None, help="annotation JSON of the NUSCENES dataset (default: annos/nuScenes_val.json)")
     add("--eager", action="store_true", help="launch every step's kernels from the host instead of replaying captured graphs")
     return parser
-
-
-def seed_everything(seed):
-    """What pytorch_lightning.seed_everything seeds: Python's, numpy's and torch's generators (CPU and every GPU)."""
-    import numpy as np
-    random.seed(seed)
-    np.random.seed(seed)
-    torch.manual_seed(seed)
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed_all(seed)
 
 
 class _StageClock:
@@ -112,14 +102,7 @@ def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames
     images = SU.load_img_seq(frame_list, height, width, "cuda")
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    unique_keys = set(e.input_key for e in model.conditioner.embedders)
-    value_dict = SU.init_embedder_options(unique_keys)
-    cond_img = images[:1]
-    value_dict["cond_frames_without_noise"] = cond_img
-    value_dict["cond_aug"] = cond_aug
-    value_dict["cond_frames"] = cond_img + cond_aug * torch.randn_like(cond_img)
-    for key, value in (action_dict or {}).items():
-        value_dict[key] = value
+    value_dict = frontdoor.first_window_values(model, images, cond_aug, action_dict)
     sampler = SU.init_sampling(sampler=SU.sampler_name(sampler), guider="TrianglePredictionGuider" if n_rounds > 1 else "VanillaCFG", steps=n_steps,
                                cfg_scale=cfg_scale, num_frames=n_frames)
     sampler.graph = sampler.cfg_streams = not eager and shard is None   # (graph replay: one GPU, no frame shard)
@@ -145,7 +128,7 @@ def init_distributed(n_frames):
     -> (global rank, shard). The caller owns the process group (destroy_process_group)."""
     import torch.distributed as dist
     from .parallel import DistComm, make_shard
-    world, rank = int(os.environ["WORLD_SIZE"]), int(os.environ.get("RANK", "0"))
+    world = int(os.environ["WORLD_SIZE"])
     mode = os.environ.get("VISTA_SHARD") or "hybrid"
     if mode not in ("hybrid", "frames"):
         raise ValueError(f"VISTA_SHARD must be 'hybrid' or 'frames', not {mode!r}")
@@ -153,14 +136,7 @@ def init_distributed(n_frames):
     if group_size > n_frames:
         raise ValueError(f"WORLD_SIZE {world} (VISTA_SHARD={mode}) puts {group_size} ranks into one frame-shard group, but --n_frames is "
                          f"{n_frames}: a rank needs at least one frame")
-    backend = os.environ.get("VISTA_DIST_BACKEND", "nccl")
-    dev = int(os.environ.get("VISTA_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    torch.cuda.set_device(dev)
-    if backend == "nccl":
-        dist.init_process_group("nccl", device_id=torch.device("cuda", dev))   # "nccl" is RCCL on ROCm
-    else:
-        dist.init_process_group(backend)
+    rank, world, dev = frontdoor.join_process_group()
     try:
         def make_group(ranks):   # collective: every rank creates every group, members get a communicator
             g = dist.new_group(ranks=ranks)
@@ -169,8 +145,8 @@ def init_distributed(n_frames):
         try:
             shard.selfcheck(torch.device("cuda", dev))
         except Exception as e:  # noqa: BLE001
-            raise RuntimeError(f"[rank {rank}/{world}] multi-GPU plumbing check failed (VISTA_SHARD={mode}, backend {backend}, "
-                               f"device cuda:{dev}): {e}") from e
+            raise RuntimeError(f"[rank {rank}/{world}] multi-GPU plumbing check failed (VISTA_SHARD={mode}, backend "
+                               f"{dist.get_backend()}, device cuda:{dev}): {e}") from e
     except BaseException:
         dist.destroy_process_group()
         raise
@@ -180,8 +156,7 @@ def init_distributed(n_frames):
 def main(argv=None):
     opt, _unknown = parse_args(prog="python -m vista_amd.sample").parse_known_args(argv)
     # sizes the kernels cannot take are refused here, before 2.5 billion parameters are built
-    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
-    SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, net_params)
+    SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, frontdoor.net_params(opt))
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:   # one rank of a torch.distributed.run job
@@ -196,39 +171,17 @@ def main(argv=None):
 
 def _sample_loop(opt, shard, rank):
     """The loop of sample.py:204-274. Every rank of a job walks the same sample indices (the walk is a function of the seed); rank 0 writes."""
-    if opt.low_vram and rank == 0:
-        print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
-    spec = dict(SU.VERSION2SPECS[opt.version])
-    if opt.config:
-        spec["config"] = opt.config
-    if opt.ckpt:
-        spec["ckpt"] = opt.ckpt
-    model = SU.init_model(spec)
-    virtual_path, real_path = os.path.join(opt.save, "virtual"), os.path.join(opt.save, "real")
-
-    sample_index = 0
-    while sample_index >= 0:
-        seed_everything(opt.seed)
-        frame_list, sample_index, dataset_length, action_dict = SU.get_sample(sample_index, opt.dataset, opt.n_frames, opt.action,
-                                                                              data_root=opt.data_root, anno_file=opt.anno_file)
+    model = frontdoor.build_model(opt, rank)
+    for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt):
         timings = {}
         samples, samples_z, inputs = run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames,
                                          n_rounds=opt.n_rounds, n_conds=opt.n_conds, n_steps=opt.n_steps, cfg_scale=opt.cfg_scale,
                                          cond_aug=opt.cond_aug, eager=opt.eager, timings=timings, shard=shard)
         if rank == 0:
             t0 = time.perf_counter()
-            for path, frames in ((virtual_path, samples), (real_path, inputs)):
-                for mode in ("videos", "grids", "images"):
-                    SU.perform_save_locally(path, frames, mode, opt.dataset, sample_index)
+            frontdoor.save_pictures(opt.save, opt.dataset, sample_index, virtual=samples, real=inputs)
             timings["save"] = time.perf_counter() - t0
-            print(f"sample {sample_index}: " + ", ".join(f"{k} {v:.2f} s" for k, v in timings.items()), flush=True)
-
-        if opt.rand_gen:
-            sample_index += random.randint(1, max(1, dataset_length - 1))
-        else:
-            sample_index += 1
-            if dataset_length <= sample_index:
-                sample_index = -1
+            print(f"sample {sample_index}: " + frontdoor.timings_text(timings), flush=True)
     return 0
 
 

@@ -27,18 +27,17 @@ larger -- null where none of the budgets swept gets there.
 Not measured: quality. The distance to a converged run of the same model says how much of the sampler's own error is left, not how good the
 picture is. Not built: rollouts (--n_rounds must be 1) and several GPUs (WORLD_SIZE > 1), refused by name. The still IMG dataset is allowed.
 """
-import json
 import math
-import os
-import random
 import sys
 import time
 
-from . import config, fidelity, sample
+from . import fidelity, frontdoor, sample
+from .frontdoor import json_number, mean
 from . import sample_utils as SU
 
 DEFAULT_SAMPLERS = "EulerEDMSampler,DPMPP2MSampler"
 DEFAULT_BUDGETS = "10,15,20,30,50"
+RECORDS_NAME, SUMMARY_NAME = "steps.jsonl", "steps_summary.json"
 RUN_FIELDS = ("sampler", "steps", "latent_err", "frame_err", "mean_psnr", "mean_ssim", "seconds")
 
 
@@ -103,18 +102,8 @@ def check_run(opt, net_params=None):
                          "results, so their errors do not separate); give --n_rounds 1")
     if opt.n_conds >= opt.n_frames:
         raise ValueError(f"--n_conds {opt.n_conds} with --n_frames {opt.n_frames}: every frame would be a conditioning frame, nothing is left to compare")
-    if opt.n_scenes < 0:
-        raise ValueError(f"--n_scenes {opt.n_scenes}: a count of scenes, or 0 for the whole dataset")
-    if opt.n_scenes == 0 and opt.rand_gen:
-        raise ValueError("--n_scenes 0 (to the end of the dataset) with the random walk: the reference's random walk never ends by itself; "
-                         "give --n_scenes N, or --rand_gen for the sequential walk")
+    frontdoor.check_scene_count(opt)
     return samplers, budgets
-
-
-def check_world():
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise ValueError(f"WORLD_SIZE {os.environ['WORLD_SIZE']}: vista_amd.step_sweep runs on one GPU (scene-per-rank sweeping with a merge of "
-                         "the records is not built); start it without torch.distributed.run")
 
 
 class SweepReport:
@@ -128,18 +117,9 @@ class SweepReport:
         return f"SweepReport({self.__dict__})"
 
 
-def _num(v):
-    v = float(v)
-    return v if math.isfinite(v) else None
-
-
-def _mean(values):
-    return math.fsum(values) / len(values) if values else float("nan")
-
-
 def clip_error(frame_err, cond):
     """The clip's figure: the mean of the per-frame errors over the frames that are not conditioning frames."""
-    return _mean([float(v) for i, v in enumerate(frame_err) if i not in set(cond)])
+    return mean([float(v) for i, v in enumerate(frame_err) if i not in set(cond)])
 
 
 def other_sampler(name):
@@ -164,14 +144,7 @@ def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames
     cond = list(range(n_conds))
     with torch.no_grad(), model.ema_scope("Sampling"):
         images = SU.load_img_seq(frame_list, height, width, "cuda")
-        unique_keys = set(e.input_key for e in model.conditioner.embedders)
-        value_dict = SU.init_embedder_options(unique_keys)
-        cond_img = images[:1]
-        value_dict["cond_frames_without_noise"] = cond_img
-        value_dict["cond_aug"] = cond_aug
-        value_dict["cond_frames"] = cond_img + cond_aug * torch.randn_like(cond_img)
-        for key, value in (action_dict or {}).items():
-            value_dict[key] = value
+        value_dict = frontdoor.first_window_values(model, images, cond_aug, action_dict)
         condition = getattr(model, "condition_fn", None) or SU.get_condition
         c, uc = condition(model, value_dict, n_frames, sample.UC_KEYS, "cuda")
         z = model.encode_first_stage(images)
@@ -203,7 +176,7 @@ def run(model, frame_list, action_dict=None, *, height=576, width=1024, n_frames
             rep = fidelity.frame_metrics(u8, u8_ref)
             pred = [i for i in range(len(frame_err)) if i not in cond]
             return {"sampler": name, "steps": int(steps), "latent_err": clip_error(frame_err, cond), "frame_err": frame_err,
-                    "mean_psnr": _num(_mean([float(rep.psnr[i]) for i in pred])), "mean_ssim": _num(_mean([float(rep.ssim[i]) for i in pred])),
+                    "mean_psnr": json_number(mean([float(rep.psnr[i]) for i in pred])), "mean_ssim": json_number(mean([float(rep.ssim[i]) for i in pred])),
                     "seconds": seconds}
 
         ref_gap = measure(other_sampler(ref_sampler), ref_steps)["latent_err"]
@@ -221,25 +194,10 @@ def settings_of(opt):
 def make_record(index, frame_list, report, settings):
     return {"index": int(index), "frames": [frame_list[0]], "seed": int(settings["seed"]), "settings": settings, "cond": [int(i) for i in report.cond],
             "ref_sampler": report.ref_sampler, "ref_steps": int(report.ref_steps), "ref_seconds": round(float(report.ref_seconds), 4),
-            "ref_gap": _num(report.ref_gap),
-            "runs": [{"sampler": r["sampler"], "steps": int(r["steps"]), "latent_err": _num(r["latent_err"]),
-                      "frame_err": [_num(v) for v in r["frame_err"]], "mean_psnr": r["mean_psnr"], "mean_ssim": r["mean_ssim"],
+            "ref_gap": json_number(report.ref_gap),
+            "runs": [{"sampler": r["sampler"], "steps": int(r["steps"]), "latent_err": json_number(r["latent_err"]),
+                      "frame_err": [json_number(v) for v in r["frame_err"]], "mean_psnr": r["mean_psnr"], "mean_ssim": r["mean_ssim"],
                       "seconds": round(float(r["seconds"]), 4)} for r in report.runs]}
-
-
-def start_records(save_dir):
-    """An empty <save_dir>/steps.jsonl: the file describes one run, as the summary does. Returns its path."""
-    os.makedirs(save_dir, exist_ok=True)
-    path = os.path.join(save_dir, "steps.jsonl")
-    open(path, "w").close()
-    return path
-
-
-def append_record(save_dir, record):
-    path = os.path.join(save_dir, "steps.jsonl")
-    with open(path, "a") as f:
-        f.write(json.dumps(record, allow_nan=False) + "\n")
-    return path
 
 
 def summarise(records):
@@ -260,8 +218,8 @@ def summarise(records):
 
         def mean_of(field):
             vals = [r[field] for _rec, r in rows]
-            return None if any(v is None for v in vals) else _num(_mean(vals))
-        runs.append({"sampler": name, "steps": steps, "scenes": len(rows), "latent_err": _num(_mean(errs)), "mean_psnr": mean_of("mean_psnr"),
+            return None if any(v is None for v in vals) else json_number(mean(vals))
+        runs.append({"sampler": name, "steps": steps, "scenes": len(rows), "latent_err": json_number(mean(errs)), "mean_psnr": mean_of("mean_psnr"),
                      "mean_ssim": mean_of("mean_ssim"), "seconds": mean_of("seconds")})
     names = []
     for name, _steps in keys:
@@ -279,16 +237,7 @@ def summarise(records):
         table.append({"sampler": row["sampler"], "steps": row["steps"], "latent_err": row["latent_err"], "matched_by": matched})
     gaps = [rec.get("ref_gap") for rec in records]
     return {"scenes": len(records), "ref_sampler": records[0].get("ref_sampler"), "ref_steps": records[0].get("ref_steps"),
-            "ref_gap": None if any(g is None for g in gaps) else _num(_mean(gaps)), "runs": runs, "equal_error": table}
-
-
-def write_summary(save_dir, records):
-    os.makedirs(save_dir, exist_ok=True)
-    path = os.path.join(save_dir, "steps_summary.json")
-    with open(path, "w") as f:
-        json.dump(summarise(records), f, allow_nan=False, indent=1)
-        f.write("\n")
-    return path
+            "ref_gap": None if any(g is None for g in gaps) else json_number(mean(gaps)), "runs": runs, "equal_error": table}
 
 
 def _scene_line(record):
@@ -300,47 +249,25 @@ def _scene_line(record):
 def main(argv=None):
     opt, _unknown = parse_args(prog="python -m vista_amd.step_sweep").parse_known_args(argv)
     # what cannot run is refused here, before 2.5 billion parameters are built
-    net_params = (config.load_config(opt.config)["model"]["params"]["network_config"]["params"] if opt.config else None)
-    samplers, budgets = check_run(opt, net_params)
-    check_world()
+    samplers, budgets = check_run(opt, frontdoor.net_params(opt))
+    frontdoor.check_world("step_sweep", "scene-per-rank sweeping with a merge of the records is not built")
     return _sweep_loop(opt, samplers, budgets)
 
 
 def _sweep_loop(opt, samplers, budgets):
     """The walk of vista_amd.sample over the dataset with the sweep behind every scene."""
-    if opt.low_vram:
-        print("--low_vram: accepted, no effect (every stage stays resident in HBM)")
-    spec = dict(SU.VERSION2SPECS[opt.version])
-    if opt.config:
-        spec["config"] = opt.config
-    if opt.ckpt:
-        spec["ckpt"] = opt.ckpt
-    model = SU.init_model(spec)
-    start_records(opt.save)
+    model = frontdoor.build_model(opt)
+    frontdoor.start_records(opt.save, RECORDS_NAME)
     records, settings = [], settings_of(opt)
-
-    sample_index = 0
-    while sample_index >= 0:
-        sample.seed_everything(opt.seed)
-        frame_list, sample_index, dataset_length, action_dict = SU.get_sample(sample_index, opt.dataset, opt.n_frames, opt.action,
-                                                                              data_root=opt.data_root, anno_file=opt.anno_file)
+    for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt, n_scenes=opt.n_scenes):
         report = run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames, n_conds=opt.n_conds,
                      cfg_scale=opt.cfg_scale, cond_aug=opt.cond_aug, eager=opt.eager, seed=opt.seed, samplers=samplers, budgets=budgets,
                      ref_steps=opt.ref_steps, ref_sampler=opt.ref_sampler)
         record = make_record(sample_index, frame_list, report, settings)
-        append_record(opt.save, record)
+        frontdoor.append_record(opt.save, RECORDS_NAME, record)
         records.append(record)
         print(_scene_line(record), flush=True)
-
-        if opt.n_scenes and len(records) >= opt.n_scenes:
-            break
-        if opt.rand_gen:
-            sample_index += random.randint(1, max(1, dataset_length - 1))
-        else:
-            sample_index += 1
-            if dataset_length <= sample_index:
-                sample_index = -1
-    write_summary(opt.save, records)
+    frontdoor.write_summary(opt.save, SUMMARY_NAME, summarise(records))
     return 0
 
 
