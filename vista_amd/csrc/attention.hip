@@ -24,7 +24,7 @@
 //   made of whole 256-row blocks (levels 0 / 1). For this kernel -- every other length, and the pipelined kernel's fallback -- the levers are
 //   instruction counts:
 //     * no row-maximum tree on the fast path: exponentials are taken against the EXISTING base and the tile is validated afterwards
-//       through its row sums; a tile that fails is redone with a re-base (see "MAX-FREE FAST PATH" in the kernel)
+//       through its row sums; a tile that fails is redone with a re-base (see "MAX-FREE FAST PATH" at OnlineSoftmax::tile)
 //     * row sums from the bf16-rounded probabilities, two per v_dot2c_f32_bf16
 //     * the lane-pair maximum of the slow path through v_permlane32_swap (VALU) instead of ds_bpermute
 //     * no s_setprio flips (measured +1.9 % without them)
@@ -34,6 +34,19 @@
 //   vwm/modules/video_attention.py:116-127, attention.py:384-399): one wave per (batch, pixel, head); Q/K
 //   fragments are loaded straight from HBM (rows are frames, stride S*ld), V goes through a 4 KiB wave-private
 //   LDS tile and is gathered in the accumulator's key order. HBM-bound by construction (12.5 FLOP/B).
+//
+// Shared pieces and their users (body = attn_spatial_body, i.e. every attn_spatial_kernel and the pipelined kernel's fallback; pipe =
+// attn_spatial_pipe_kernel; fp8 = attn_spatial_fp8qk_kernel; temporal = attn_temporal_kernel):
+//   OnlineSoftmax<QW, PRE> (probabilities, rebase, the max-free tile step, 1 / l)   body, fp8 -- each passes its own score product
+//   mask_tail_keys (ragged last tile)                                               body, fp8
+//   v_frag_tr (transposing V^T fragment read)                                       body (VROW), pipe, fp8
+//   store_rows8 (normalise, 8-byte stores)                                          body, fp8 (bf16 output), temporal (narrow rows)
+//   norm_wide (normalise, widen_pair of common.h, 16-byte stores)                   pipe, temporal (WIDE)
+//   mx_quant_block (common.h, shared with the GEMM epilogues)                       fp8 (MX-fp8 output)
+//   attn_seq_class / attn_class_rows / attn_rescale_thr                             both spatial launchers
+// Still written per kernel, on purpose: the query-row setup (qrow / q_ok), the row-major V staging offsets (v_chunk / v_off) and the
+// per-lane base of the transposing V read (vtr_base / vtr0) of body, fp8 and pipe. As shared functions each of them changed the address
+// arithmetic the compiler emits for the pipelined kernel and the 512-row kernels (profiles/attention_shared_core.txt, part A).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -53,32 +66,7 @@ __device__ __forceinline__ bf16x8_t make_frag(uint2 a, uint2 b) {
     return __builtin_bit_cast(bf16x8_t, v);
 }
 
-__device__ uint4 g_attn_zero16;
-
-// MX-fp8 quantisation of one 32-element block held as four accumulator quads across the lane pair (l, l ^ 32): see mx_quant_block in gemm_common.h
-__device__ __forceinline__ uint4 mx_quant_block_attn(const float (&v)[4][4], int& e8m0) {
-    float amax = 0.f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fabsf(v[g][e]));
-    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-    int ex = -127;
-    if (amax > 0.f) frexpf(amax * (1.f / 448.f), &ex);
-    ex = ex < -127 ? -127 : (ex > 127 ? 127 : ex);
-    const float inv = ldexpf(1.f, -ex);
-    uint32_t q[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[g][0] * inv, v[g][1] * inv, 0, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(v[g][2] * inv, v[g][3] * inv, w, true);
-        q[g] = (uint32_t)w;
-    }
-    const auto r02 = __builtin_amdgcn_permlane32_swap(q[0], q[2], false, false);
-    const auto r13 = __builtin_amdgcn_permlane32_swap(q[1], q[3], false, false);
-    e8m0 = ex + 127;
-    return make_uint4(r02[0], r02[1], r13[0], r13[1]);
-}  // zero source for keys past the end of the sequence (LDS-DMA cannot predicate its write)
+__device__ uint4 g_attn_zero16;  // zero source for keys past the end of the sequence (LDS-DMA cannot predicate its write)
 
 // actual key (within a 32-key subtile) held by K-tile LDS row rho: bits [g1 g0 h e1 e0] -> [g1 h g0 e1 e0].
 // With this row permutation the accumulator registers 8*(J&1)..+7 of lane-half h hold the 8 CONTIGUOUS keys 16J + 8h + 0..7,
@@ -99,6 +87,182 @@ __device__ __forceinline__ float dot2_ones(uint32_t packed, float acc) {  // acc
     const bf16x2v_t one = {(__bf16)1.0f, (__bf16)1.0f};
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v_t, packed), one, acc, false);
 }
+
+// ---- pieces shared by the spatial kernels (attn_spatial_body, attn_spatial_pipe_kernel, attn_spatial_fp8qk_kernel) ----
+
+// Transposing read of a V^T fragment (A operand of the PV MFMA: row d, 8 consecutive keys) from a row-major V tile at p = tile + the lane's
+// base for the d half + J * 2048 for the k-step (the bases: "VROW fragment reads" in attn_spatial_body): keys +0..3 and, 512 bytes on, +4..7.
+__device__ __forceinline__ bf16x8_t v_frag_tr(const char* p) {   // two ds_read_b64_tr_b16
+    typedef short s4_t __attribute__((ext_vector_type(4)));
+    typedef s4_t __attribute__((address_space(3))) * lds_s4_t;
+    const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)p);
+    const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(p + 512));
+    bf16x8_t f;
+    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
+    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
+    return f;
+}
+
+// Ragged last tile (the caller's test): keys past the end of the sequence get a score of NEG_BIG. Accumulator row
+// rho32 = (r&3) + 8*(r>>2) + 4*lh holds key key_of_row(rho32) of subtile c. (Scalars by reference, as the `scores` lambdas hold them: taken by value the 32 comparisons are folded
+// over lh early and the block grows by 22 scalar ORs -- profiles/attention_shared_core.txt.)
+template <int QW>
+__device__ __forceinline__ void mask_tail_keys(f32x16_t (&sacc)[QW][2], const int& t, const int& S, const int& lh) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = t * 64 + c * 32 + key_of_row((r & 3) + 8 * (r >> 2) + 4 * lh);
+            if (key >= S) {
+#pragma unroll
+                for (int b = 0; b < QW; ++b) sacc[b][c][r] = NEG_BIG;
+            }
+        }
+}
+
+// Output of one 32-row block: lane (l31, lh) holds d = 32 dd + 8 g + 4 lh + e of row l31 in acc[dd][4 g + e]. norm_quad = quad g times inv,
+// packed to the storage type (8 bytes); store_rows8 writes a row's 16 quads that way (optr = the row's d = 4 lh); norm_wide = quads 2 gp and
+// 2 gp + 1 through widen_pair (common.h), the lane's 16 bytes at d = 32 dd + 16 gp + 8 lh.
+__device__ __forceinline__ uint2 norm_quad(const f32x16_t& acc, const int g, const float inv) {
+    uint2 w;
+    w.x = pack_bf16(acc[4 * g + 0] * inv, acc[4 * g + 1] * inv);
+    w.y = pack_bf16(acc[4 * g + 2] * inv, acc[4 * g + 3] * inv);
+    return w;
+}
+__device__ __forceinline__ void store_rows8(uint16_t* optr, const f32x16_t (&acc)[2], const float inv) {
+#pragma unroll
+    for (int d = 0; d < 2; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *(uint2*)(optr + 32 * d + 8 * g) = norm_quad(acc[d], g, inv);
+}
+__device__ __forceinline__ uint4 norm_wide(const f32x16_t& acc, const int gp, const float inv) {
+    return widen_pair(norm_quad(acc, 2 * gp, inv), norm_quad(acc, 2 * gp + 1, inv));
+}
+
+// The online softmax of one wave's QW 32-row query blocks over the 64-key tiles of a K loop: shared by attn_spatial_body and
+// attn_spatial_fp8qk_kernel, which differ only in how a tile's scores are produced (the `scores` callable of tile(): it fills sacc, S^T of
+// the tile, ragged tail masked). A lane's 32 scores of a block all belong to query column l31; the lane pair (l, l ^ 32) shares the column.
+// PRE: a score is already the base-2 exponent (see attn_spatial_body); otherwise it is multiplied by scale_log2 first.
+template <int QW, bool PRE>
+struct OnlineSoftmax {
+    float m_run[QW], l_run[QW];   // running base (base-2 exponent) and row sum under it, per query block
+    bool zero_base;               // PRE: every row of this wave uses base 0 (wave-uniform)
+
+    __device__ __forceinline__ void start(f32x16_t (&oacc)[QW][2]) {
+#pragma unroll
+        for (int b = 0; b < QW; ++b) {
+            m_run[b] = NEG_BIG;
+            l_run[b] = 0.f;
+#pragma unroll
+            for (int d = 0; d < 2; ++d)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) oacc[b][d][r] = 0.f;
+        }
+        zero_base = false;
+    }
+    // the row-sum bound of the fast path's validation (see tile()); finite whatever the tuning value: an overflowed row sum (+inf) must fail the test
+    static __device__ __forceinline__ float psum_limit(float rescale_thr) { return PRE ? 0x1p100f : fast_exp2(fminf(rescale_thr, 100.f) + 5.f); }
+
+    // ---- probabilities under the CURRENT base m_run. P^T fragments: k-step J = accumulator regs 8*(J&1)..+7 of key subtile J>>1 = keys
+    //      16J + 8*lh + 0..7. The row sum is taken from the ROUNDED probabilities, two per v_dot2c_f32_bf16 (half the adds, and l matches
+    //      what the PV MFMAs accumulate). ZB: base zero, the probability is v_exp_f32 of the score itself ----
+    template <bool ZB>
+    __device__ __forceinline__ void probabilities(f32x16_t (&sacc)[QW][2], bf16x8_t (&pf)[QW][4], float (&psum)[QW], const float scale_log2) const {
+#pragma unroll
+        for (int b = 0; b < QW; ++b) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sacc[b][c][r] = fast_exp2(ZB ? sacc[b][c][r] : (PRE ? sacc[b][c][r] - m_run[b] : fmaf(sacc[b][c][r], scale_log2, -m_run[b])));
+            psum[b] = 0.f;
+#pragma unroll
+            for (int J = 0; J < 4; ++J) {
+                const int c = J >> 1, r0 = 8 * (J & 1);
+                uint4 v;
+                v.x = pack_bf16x(sacc[b][c][r0 + 0], sacc[b][c][r0 + 1]);
+                v.y = pack_bf16x(sacc[b][c][r0 + 2], sacc[b][c][r0 + 3]);
+                v.z = pack_bf16x(sacc[b][c][r0 + 4], sacc[b][c][r0 + 5]);
+                v.w = pack_bf16x(sacc[b][c][r0 + 6], sacc[b][c][r0 + 7]);
+                psum[b] = dot2_ones(v.x, psum[b]);
+                psum[b] = dot2_ones(v.y, psum[b]);
+                psum[b] = dot2_ones(v.z, psum[b]);
+                psum[b] = dot2_ones(v.w, psum[b]);
+                pf[b][J] = __builtin_bit_cast(bf16x8_t, v);
+            }
+        }
+    }
+
+    // ---- re-base on this tile's row maxima: m_run <- max(m_run, max_keys s), O and l scaled to the new base ----
+    __device__ __forceinline__ void rebase(const f32x16_t (&sacc)[QW][2], f32x16_t (&oacc)[QW][2], const float scale_log2) {
+#pragma unroll
+        for (int b = 0; b < QW; ++b) {
+            float mx = sacc[b][0][0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[b][0][r]);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[b][1][r]);
+            mx = fmaxf(PRE ? pair_max(mx) : pair_max(mx) * scale_log2, NEG_BIG);
+            float m_new = fmaxf(m_run[b], mx);
+            if (PRE && fabsf(m_new) <= 60.f) m_new = 0.f;
+            const float alpha = fast_exp2(m_run[b] - m_new);
+            m_run[b] = m_new;
+            l_run[b] *= alpha;
+#pragma unroll
+            for (int d = 0; d < 2; ++d)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) oacc[b][d][r] *= alpha;
+        }
+        if constexpr (PRE) {
+            bool z = m_run[0] == 0.f;
+#pragma unroll
+            for (int b = 1; b < QW; ++b) z = z && (m_run[b] == 0.f);
+            zero_base = __all(z);
+        }
+    }
+
+    // One 64-key tile: scores() -> sacc, bf16 probabilities -> pf (B operands of the PV MFMAs), l_run advanced, oacc re-based where needed.
+    // sacc, pf and psum (the tile's row sums: scratch of this step) are the CALLER's loop-body locals -- declared inside tile(), psum alone
+    // changes how the two probability paths of the PRE kernels are merged (241 -> 252 VGPRs in the 512-row kernel, part A of
+    // profiles/attention_shared_core.txt).
+    // MAX-FREE FAST PATH. The loop costs close to the SUM of its VALU and MFMA issue time (profiles/r02_attn_ablation.txt), and the
+    // row-maximum tree is ~30 of its ~150 VALU instructions per tile -- for a result that changes nothing on almost every tile:
+    // after the first tiles a row's maximum hardly ever grows by more than a few octaves. So the exponentials are taken against
+    // the EXISTING base without looking at the maximum, and the tile is validated AFTERWARDS through the row sum it needs anyway:
+    // if some lane's 32 probabilities sum to more than 2^(thr+5) (one of them exceeded the old maximum by > 2^thr..2^(thr+5);
+    // +inf / NaN from an overflowing exp2 fail the <= test too), the tile is redone the slow way -- scores recomputed from the
+    // K tile still in LDS, re-base on their maxima, probabilities again. fp32 exp2 cannot overflow before the score exceeds the
+    // base by 128 octaves, bf16 P and the fp32 accumulators keep their RELATIVE precision whatever the common factor, and the
+    // final division by l removes it. Tile 0 always takes the slow path (it defines the first base).
+    template <class Scores>
+    __device__ __forceinline__ void tile(const int t, Scores& scores, f32x16_t (&sacc)[QW][2], bf16x8_t (&pf)[QW][4], f32x16_t (&oacc)[QW][2], const float scale_log2,
+                                         const float psum_limit, float (&psum)[QW]) {
+        scores();
+        if (__builtin_expect(t == 0, 0)) rebase(sacc, oacc, scale_log2);
+        if constexpr (PRE) {
+            if (zero_base) probabilities<true>(sacc, pf, psum, scale_log2);
+            else probabilities<false>(sacc, pf, psum, scale_log2);
+        } else {
+            probabilities<false>(sacc, pf, psum, scale_log2);
+        }
+        bool bad = !(psum[0] <= psum_limit);
+#pragma unroll
+        for (int b = 1; b < QW; ++b) bad = bad || !(psum[b] <= psum_limit);
+        if (__builtin_expect(__any(bad), 0)) {  // wave-uniform, rare
+            asm volatile("" ::: "memory");  // re-read the fragments: keeping the fast path's copies alive for this branch costs spills
+            scores();
+            rebase(sacc, oacc, scale_log2);
+            probabilities<false>(sacc, pf, psum, scale_log2);  // (the general form is right for any base, zero included)
+        }
+#pragma unroll
+        for (int b = 0; b < QW; ++b) l_run[b] += psum[b];
+    }
+
+    // 1 / l of query block b's rows, the lane pair's halves of the row sum combined
+    __device__ __forceinline__ float inv_row_sum(int b) const {
+        const float l_tot = l_run[b] + __shfl_xor(l_run[b], 32, 64);
+        return 1.f / l_tot;
+    }
+};
 
 // NW waves per workgroup, QW 32-row query blocks per wave: NW*QW*32 query rows share each 64-key K / V^T tile. QW = 2 (long sequences)
 // feeds every K / V^T fragment read to TWO MFMAs: the K-loop of these kernels is LDS-throughput-bound (profiles/r02_ab_notes.txt A/B 2),
@@ -217,35 +381,16 @@ __device__ __forceinline__ void attn_spatial_body(char* const smem, const int lo
         vtr_base[1] = b0 + (1 ^ sw1) * 64;
     }
     auto v_frag = [&](const char* sV, int d, int J) -> bf16x8_t {
-        if constexpr (VROW) {
-            typedef short s4_t __attribute__((ext_vector_type(4)));
-            typedef s4_t __attribute__((address_space(3))) * lds_s4_t;
-            const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(sV + vtr_base[d] + J * 2048));
-            const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(sV + vtr_base[d] + J * 2048 + 512));
-            bf16x8_t f;
-            f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-            f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-            return f;
-        } else {
-            return *(const bf16x8_t*)(sV + d * 32 * 128 + frag_off[J]);
-        }
+        if constexpr (VROW) return v_frag_tr(sV + vtr_base[d] + J * 2048);
+        else return *(const bf16x8_t*)(sV + d * 32 * 128 + frag_off[J]);
     };
 
     f32x16_t oacc[QW][2];
-    float m_run[QW], l_run[QW];
-#pragma unroll
-    for (int b = 0; b < QW; ++b) {
-        m_run[b] = NEG_BIG;
-        l_run[b] = 0.f;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[b][d][r] = 0.f;
-    }
+    OnlineSoftmax<QW, PRE> sm;
+    sm.start(oacc);
+    const float psum_limit = sm.psum_limit(rescale_thr);
 
     const int nt = n_tiles;
-    const float psum_limit = PRE ? 0x1p100f : fast_exp2(fminf(rescale_thr, 100.f) + 5.f);  // finite whatever the tuning value: an overflowed row sum (+inf) must fail the test
-    bool zero_base = false;  // PRE: every row of this wave uses base 0 (wave-uniform)
     dma_tile(0, 0);
     __syncthreads();
 
@@ -257,7 +402,6 @@ __device__ __forceinline__ void attn_spatial_body(char* const smem, const int lo
 
         f32x16_t sacc[QW][2];
         bf16x8_t pf[QW][4];
-        float psum[QW];
         // ---- S^T[key][q] = K . Q^T : every K fragment feeds the QW query blocks of the wave ----
         auto scores = [&]() {
 #pragma unroll
@@ -273,107 +417,10 @@ __device__ __forceinline__ void attn_spatial_body(char* const smem, const int lo
                     for (int b = 0; b < QW; ++b) sacc[b][c] = vk_mfma(kf, qf[b][ks], sacc[b][c]);
                 }
             }
-            if (t == nt - 1 && (S & 63)) {  // mask keys past the end of the sequence (last tile only)
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        // accumulator row rho32 = (r&3) + 8*(r>>2) + 4*lh holds key key_of_row(rho32) of subtile c
-                        const int key = t * 64 + c * 32 + key_of_row((r & 3) + 8 * (r >> 2) + 4 * lh);
-                        if (key >= S) {
-#pragma unroll
-                            for (int b = 0; b < QW; ++b) sacc[b][c][r] = NEG_BIG;
-                        }
-                    }
-            }
+            if (t == nt - 1 && (S & 63)) mask_tail_keys<QW>(sacc, t, S, lh);  // (last tile only)
         };
-        // ---- probabilities under the CURRENT base m_run: the lane's 32 scores all belong to query column l31. P^T fragments: k-step
-        //      J = accumulator regs 8*(J&1)..+7 of key subtile J>>1 = keys 16J + 8*lh + 0..7. The row sum is taken from the ROUNDED
-        //      probabilities, two per v_dot2c_f32_bf16 (half the adds, and l matches what the PV MFMAs accumulate) ----
-        auto probabilities = [&](auto zb_tag) __attribute__((always_inline)) {
-            constexpr bool ZB = decltype(zb_tag)::value;
-#pragma unroll
-            for (int b = 0; b < QW; ++b) {
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sacc[b][c][r] = fast_exp2(ZB ? sacc[b][c][r] : (PRE ? sacc[b][c][r] - m_run[b] : fmaf(sacc[b][c][r], scale_log2, -m_run[b])));
-                psum[b] = 0.f;
-#pragma unroll
-                for (int J = 0; J < 4; ++J) {
-                    const int c = J >> 1, r0 = 8 * (J & 1);
-                    uint4 v;
-                    v.x = pack_bf16x(sacc[b][c][r0 + 0], sacc[b][c][r0 + 1]);
-                    v.y = pack_bf16x(sacc[b][c][r0 + 2], sacc[b][c][r0 + 3]);
-                    v.z = pack_bf16x(sacc[b][c][r0 + 4], sacc[b][c][r0 + 5]);
-                    v.w = pack_bf16x(sacc[b][c][r0 + 6], sacc[b][c][r0 + 7]);
-                    psum[b] = dot2_ones(v.x, psum[b]);
-                    psum[b] = dot2_ones(v.y, psum[b]);
-                    psum[b] = dot2_ones(v.z, psum[b]);
-                    psum[b] = dot2_ones(v.w, psum[b]);
-                    pf[b][J] = __builtin_bit_cast(bf16x8_t, v);
-                }
-            }
-        };
-        // ---- re-base of the online softmax on this tile's row maxima: m_run <- max(m_run, max_keys s), O and l scaled to the new base ----
-        auto rebase = [&]() {
-#pragma unroll
-            for (int b = 0; b < QW; ++b) {
-                float mx = sacc[b][0][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[b][0][r]);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[b][1][r]);
-                mx = fmaxf(PRE ? pair_max(mx) : pair_max(mx) * scale_log2, NEG_BIG);
-                float m_new = fmaxf(m_run[b], mx);
-                if (PRE && fabsf(m_new) <= 60.f) m_new = 0.f;
-                const float alpha = fast_exp2(m_run[b] - m_new);
-                m_run[b] = m_new;
-                l_run[b] *= alpha;
-#pragma unroll
-                for (int d = 0; d < 2; ++d)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) oacc[b][d][r] *= alpha;
-            }
-            if constexpr (PRE) {
-                bool z = m_run[0] == 0.f;
-#pragma unroll
-                for (int b = 1; b < QW; ++b) z = z && (m_run[b] == 0.f);
-                zero_base = __all(z);
-            }
-        };
-        auto probs = [&]() __attribute__((always_inline)) {
-            if constexpr (PRE) {
-                if (zero_base) probabilities(std::true_type{});
-                else probabilities(std::false_type{});
-            } else {
-                probabilities(std::false_type{});
-            }
-        };
-
-        // MAX-FREE FAST PATH. The loop costs close to the SUM of its VALU and MFMA issue time (profiles/r02_attn_ablation.txt), and the
-        // row-maximum tree is ~30 of its ~150 VALU instructions per tile -- for a result that changes nothing on almost every tile:
-        // after the first tiles a row's maximum hardly ever grows by more than a few octaves. So the exponentials are taken against
-        // the EXISTING base without looking at the maximum, and the tile is validated AFTERWARDS through the row sum it needs anyway:
-        // if some lane's 32 probabilities sum to more than 2^(thr+5) (one of them exceeded the old maximum by > 2^thr..2^(thr+5);
-        // +inf / NaN from an overflowing exp2 fail the <= test too), the tile is redone the slow way -- scores recomputed from the
-        // K tile still in LDS, re-base on their maxima, probabilities again. fp32 exp2 cannot overflow before the score exceeds the
-        // base by 128 octaves, bf16 P and the fp32 accumulators keep their RELATIVE precision whatever the common factor, and the
-        // final division by l removes it. Tile 0 always takes the slow path (it defines the first base).
-        scores();
-        if (__builtin_expect(t == 0, 0)) rebase();
-        probs();
-        bool bad = !(psum[0] <= psum_limit);
-#pragma unroll
-        for (int b = 1; b < QW; ++b) bad = bad || !(psum[b] <= psum_limit);
-        if (__builtin_expect(__any(bad), 0)) {  // wave-uniform, rare
-            asm volatile("" ::: "memory");  // re-read the fragments: keeping the fast path's copies alive for this branch costs spills
-            scores();
-            rebase();
-            probabilities(std::false_type{});  // (the general form is right for any base, zero included)
-        }
-#pragma unroll
-        for (int b = 0; b < QW; ++b) l_run[b] += psum[b];
+        float psum[QW];  // (the step's scratch: see tile())
+        sm.tile(t, scores, sacc, pf, oacc, scale_log2, psum_limit, psum);
 
         // ---- O^T[d][q] += V^T . P^T : V^T fragment (row d = 32*dd + l31, keys 16J + 8*lh ..+7) is one ds_read_b128, shared by the
         //      wave's query blocks ----
@@ -391,20 +438,8 @@ __device__ __forceinline__ void attn_spatial_body(char* const smem, const int lo
 
 #pragma unroll
     for (int b = 0; b < QW; ++b) {
-        const float l_tot = l_run[b] + __shfl_xor(l_run[b], 32, 64);
-        const float inv = 1.f / l_tot;
-        if (q_ok[b]) {
-            uint16_t* optr = o + ((size_t)img * S + qrow[b]) * ldo + head * 64 + 4 * lh;
-#pragma unroll
-            for (int d = 0; d < 2; ++d)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    uint2 w;
-                    w.x = pack_bf16(oacc[b][d][4 * g + 0] * inv, oacc[b][d][4 * g + 1] * inv);
-                    w.y = pack_bf16(oacc[b][d][4 * g + 2] * inv, oacc[b][d][4 * g + 3] * inv);
-                    *(uint2*)(optr + 32 * d + 8 * g) = w;
-                }
-        }
+        const float inv = sm.inv_row_sum(b);   // (in every lane: a cross-lane exchange)
+        if (q_ok[b]) store_rows8(o + ((size_t)img * S + qrow[b]) * ldo + head * 64 + 4 * lh, oacc[b], inv);
     }
 }
 
@@ -455,8 +490,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_spatial_pipe_kernel(const uin
     __shared__ __attribute__((aligned(16))) char smem[40960 + (ONE_PER_CU ? 48 * 1024 : 0)];
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
-    typedef short s4_t __attribute__((ext_vector_type(4)));
-    typedef s4_t __attribute__((address_space(3))) * lds_s4_t;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -534,13 +567,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_spatial_pipe_kernel(const uin
     // V fragment f = 2 * d + j of key block c: row d half d, keys 32 c + 16 j + 8 lh ... -- two transposing 8-byte reads
     auto read_v = [&](const char* sV, const int c, const int f) __attribute__((always_inline)) {
         const int d = f >> 1, J = 2 * c + (f & 1);
-        const int vb = vtr0 ^ (d << 6);
-        const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(sV + vb + J * 2048));
-        const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(sV + vb + J * 2048 + 512));
-        bf16x8_t r;
-        r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-        r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-        vf[f] = r;
+        vf[f] = v_frag_tr(sV + (vtr0 ^ (d << 6)) + J * 2048);
     };
     auto p_frag = [&](const uint32_t* w4) __attribute__((always_inline)) -> bf16x8_t {
         const uint4 u = make_uint4(w4[0], w4[1], w4[2], w4[3]);
@@ -662,16 +689,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_spatial_pipe_kernel(const uin
 #pragma unroll
         for (int d = 0; d < 2; ++d)
 #pragma unroll
-            for (int gp = 0; gp < 2; ++gp) {
-                uint2 qa, qb2;
-                qa.x = pack_bf16(oacc[b][d][8 * gp + 0] * inv[b], oacc[b][d][8 * gp + 1] * inv[b]);
-                qa.y = pack_bf16(oacc[b][d][8 * gp + 2] * inv[b], oacc[b][d][8 * gp + 3] * inv[b]);
-                qb2.x = pack_bf16(oacc[b][d][8 * gp + 4] * inv[b], oacc[b][d][8 * gp + 5] * inv[b]);
-                qb2.y = pack_bf16(oacc[b][d][8 * gp + 6] * inv[b], oacc[b][d][8 * gp + 7] * inv[b]);
-                const auto rx = __builtin_amdgcn_permlane32_swap(qa.x, qb2.x, false, false);
-                const auto ry = __builtin_amdgcn_permlane32_swap(qa.y, qb2.y, false, false);
-                *(uint4*)(optr + 32 * d + 16 * gp) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-            }
+            for (int gp = 0; gp < 2; ++gp) *(uint4*)(optr + 32 * d + 16 * gp) = norm_wide(oacc[b][d], gp, inv[b]);
     }
 }
 
@@ -800,26 +818,11 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(const uint16_t* __re
             for (int d = 0; d < 2; ++d)
 #pragma unroll
                 for (int gp = 0; gp < 2; ++gp) {
-                    uint2 qa, qb;
-                    qa.x = pack_bf16(oacc[d][8 * gp + 0] * inv, oacc[d][8 * gp + 1] * inv);
-                    qa.y = pack_bf16(oacc[d][8 * gp + 2] * inv, oacc[d][8 * gp + 3] * inv);
-                    qb.x = pack_bf16(oacc[d][8 * gp + 4] * inv, oacc[d][8 * gp + 5] * inv);
-                    qb.y = pack_bf16(oacc[d][8 * gp + 6] * inv, oacc[d][8 * gp + 7] * inv);
-                    const auto rx = __builtin_amdgcn_permlane32_swap(qa.x, qb.x, false, false);
-                    const auto ry = __builtin_amdgcn_permlane32_swap(qa.y, qb.y, false, false);
-                    if (active && t_ok) *(uint4*)(optr + 32 * d + 16 * gp) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
+                    const uint4 w = norm_wide(oacc[d], gp, inv);
+                    if (active && t_ok) *(uint4*)(optr + 32 * d + 16 * gp) = w;
                 }
         } else if (active && t_ok) {
-            uint16_t* optr = o + (row0 + (size_t)l31 * S) * ldo + head * 64 + 4 * lh;
-#pragma unroll
-            for (int d = 0; d < 2; ++d)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    uint2 w2;
-                    w2.x = pack_bf16(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv);
-                    w2.y = pack_bf16(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv);
-                    *(uint2*)(optr + 32 * d + 8 * g) = w2;
-                }
+            store_rows8(o + (row0 + (size_t)l31 * S) * ldo + head * 64 + 4 * lh, oacc, inv);
         }
         if (WSYNC) {   // this wave's reads of its tile are done before its next writes (in-order LDS; compiler pinned)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1012,18 +1015,9 @@ __global__ __launch_bounds__(NW * 64, QW == 2 ? 2 : 4) void attn_spatial_fp8qk_k
     }
 
     f32x16_t oacc[QW][2];
-    float m_run[QW], l_run[QW];
-#pragma unroll
-    for (int b = 0; b < QW; ++b) {
-        m_run[b] = NEG_BIG;
-        l_run[b] = 0.f;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[b][d][r] = 0.f;
-    }
-    const float psum_limit = PRE ? 0x1p100f : fast_exp2(fminf(rescale_thr, 100.f) + 5.f);
-    bool zero_base = false;
+    OnlineSoftmax<QW, PRE> sm;
+    sm.start(oacc);
+    const float psum_limit = sm.psum_limit(rescale_thr);
     int ksc[2], ksc_next[2];
     dma_tile(0, 0);
     k_scales(0, ksc);
@@ -1037,7 +1031,6 @@ __global__ __launch_bounds__(NW * 64, QW == 2 ? 2 : 4) void attn_spatial_fp8qk_k
 
         f32x16_t sacc[QW][2];
         bf16x8_t pf[QW][4];
-        float psum[QW];
         auto scores = [&]() __attribute__((always_inline)) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
@@ -1052,100 +1045,15 @@ __global__ __launch_bounds__(NW * 64, QW == 2 ? 2 : 4) void attn_spatial_fp8qk_k
                     sacc[b][c] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf, qf[b], z, 0, 0, 0, ksc[c], 0, qsc[b]);
                 }
             }
-            if (t == nt - 1 && (S & 63)) {
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = t * 64 + c * 32 + key_of_row((r & 3) + 8 * (r >> 2) + 4 * lh);
-                        if (key >= S) {
-#pragma unroll
-                            for (int b = 0; b < QW; ++b) sacc[b][c][r] = NEG_BIG;
-                        }
-                    }
-            }
+            if (t == nt - 1 && (S & 63)) mask_tail_keys<QW>(sacc, t, S, lh);
         };
-        auto probabilities = [&](auto zb_tag) __attribute__((always_inline)) {
-            constexpr bool ZB = decltype(zb_tag)::value;
-#pragma unroll
-            for (int b = 0; b < QW; ++b) {
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sacc[b][c][r] = fast_exp2(ZB ? sacc[b][c][r] : (PRE ? sacc[b][c][r] - m_run[b] : fmaf(sacc[b][c][r], scale_log2, -m_run[b])));
-                psum[b] = 0.f;
-#pragma unroll
-                for (int J = 0; J < 4; ++J) {
-                    const int c = J >> 1, r0 = 8 * (J & 1);
-                    uint4 w;
-                    w.x = pack_bf16x(sacc[b][c][r0 + 0], sacc[b][c][r0 + 1]);
-                    w.y = pack_bf16x(sacc[b][c][r0 + 2], sacc[b][c][r0 + 3]);
-                    w.z = pack_bf16x(sacc[b][c][r0 + 4], sacc[b][c][r0 + 5]);
-                    w.w = pack_bf16x(sacc[b][c][r0 + 6], sacc[b][c][r0 + 7]);
-                    psum[b] = dot2_ones(w.x, psum[b]);
-                    psum[b] = dot2_ones(w.y, psum[b]);
-                    psum[b] = dot2_ones(w.z, psum[b]);
-                    psum[b] = dot2_ones(w.w, psum[b]);
-                    pf[b][J] = __builtin_bit_cast(bf16x8_t, w);
-                }
-            }
-        };
-        auto rebase = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int b = 0; b < QW; ++b) {
-                float mx = sacc[b][0][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[b][0][r]);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[b][1][r]);
-                mx = fmaxf(PRE ? pair_max(mx) : pair_max(mx) * scale_log2, NEG_BIG);
-                float m_new = fmaxf(m_run[b], mx);
-                if (PRE && fabsf(m_new) <= 60.f) m_new = 0.f;
-                const float alpha = fast_exp2(m_run[b] - m_new);
-                m_run[b] = m_new;
-                l_run[b] *= alpha;
-#pragma unroll
-                for (int d = 0; d < 2; ++d)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) oacc[b][d][r] *= alpha;
-            }
-            if constexpr (PRE) {
-                bool z = m_run[0] == 0.f;
-#pragma unroll
-                for (int b = 1; b < QW; ++b) z = z && (m_run[b] == 0.f);
-                zero_base = __all(z);
-            }
-        };
-        // the bf16 kernel's max-free fast path (see attn_spatial_kernel): exponentials against the existing base, validated by the row sums
-        scores();
-        if (__builtin_expect(t == 0, 0)) rebase();
-        if constexpr (PRE) {
-            if (zero_base) probabilities(std::true_type{});
-            else probabilities(std::false_type{});
-        } else {
-            probabilities(std::false_type{});
-        }
-        bool bad = !(psum[0] <= psum_limit);
-#pragma unroll
-        for (int b = 1; b < QW; ++b) bad = bad || !(psum[b] <= psum_limit);
-        if (__builtin_expect(__any(bad), 0)) {
-            asm volatile("" ::: "memory");
-            scores();
-            rebase();
-            probabilities(std::false_type{});
-        }
-#pragma unroll
-        for (int b = 0; b < QW; ++b) l_run[b] += psum[b];
+        float psum[QW];  // (the step's scratch: see tile())
+        sm.tile(t, scores, sacc, pf, oacc, scale_log2, psum_limit, psum);
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
 #pragma unroll
             for (int J = 0; J < 4; ++J) {
-                typedef short s4_t __attribute__((ext_vector_type(4)));
-                typedef s4_t __attribute__((address_space(3))) * lds_s4_t;
-                const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(sV + vtr_base[d] + J * 2048));
-                const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(sV + vtr_base[d] + J * 2048 + 512));
-                bf16x8_t vf;
-                vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3]; vf[4] = hi[0]; vf[5] = hi[1]; vf[6] = hi[2]; vf[7] = hi[3];
+                const bf16x8_t vf = v_frag_tr(sV + vtr_base[d] + J * 2048);
 #pragma unroll
                 for (int b = 0; b < QW; ++b) oacc[b][d] = vk_mfma_bf16x(vf, pf[b][J], oacc[b][d]);
             }
@@ -1157,8 +1065,7 @@ __global__ __launch_bounds__(NW * 64, QW == 2 ? 2 : 4) void attn_spatial_fp8qk_k
 
 #pragma unroll
     for (int b = 0; b < QW; ++b) {
-        const float l_tot = l_run[b] + __shfl_xor(l_run[b], 32, 64);
-        const float inv = 1.f / l_tot;
+        const float inv = sm.inv_row_sum(b);
         const size_t row = (size_t)img * S + qrow[b];
         if (o8 != nullptr) {  // MX fp8 output: one E8M0 scale per row and 32 head-dim elements (= one accumulator set d)
 #pragma unroll
@@ -1169,7 +1076,7 @@ __global__ __launch_bounds__(NW * 64, QW == 2 ? 2 : 4) void attn_spatial_fp8qk_k
 #pragma unroll
                     for (int e = 0; e < 4; ++e) vq[g][e] = oacc[b][d][4 * g + e] * inv;
                 int e8;
-                const uint4 q16 = mx_quant_block_attn(vq, e8);
+                const uint4 q16 = mx_quant_block(vq, e8);
                 if (q_ok[b]) {
                     *(uint4*)(o8 + row * ldo8 + head * 64 + 32 * d + 16 * lh) = q16;
                     if (lh == 0) {
@@ -1180,20 +1087,22 @@ __global__ __launch_bounds__(NW * 64, QW == 2 ? 2 : 4) void attn_spatial_fp8qk_k
                 }
             }
         } else if (q_ok[b]) {
-            uint16_t* optr = o + row * ldo + head * 64 + 4 * lh;
-#pragma unroll
-            for (int d = 0; d < 2; ++d)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    uint2 w;
-                    w.x = pack_bf16(oacc[b][d][4 * g + 0] * inv, oacc[b][d][4 * g + 1] * inv);
-                    w.y = pack_bf16(oacc[b][d][4 * g + 2] * inv, oacc[b][d][4 * g + 3] * inv);
-                    *(uint2*)(optr + 32 * d + 8 * g) = w;
-                }
+            store_rows8(o + row * ldo + head * 64 + 4 * lh, oacc[b], inv);
         }
     }
 }
 }  // namespace
+
+// Sequence-length class of the spatial launchers and its query rows per workgroup. Long sequences (class 2): 8 waves x 64 query rows (512
+// per workgroup): every K / V^T fragment read feeds two MFMAs and the K/V^T stream per FLOP halves again; medium ones (1) 8 x 32 = 256;
+// short ones (0) 4 x 32 = 128 so the ragged last q-block wastes less (S = 144, 576 at the deep levels).
+static int attn_seq_class(int S) { return S >= 4096 ? 2 : (S >= 2048 ? 1 : 0); }
+static int attn_class_rows(int cls) { return cls == 2 ? 512 : (cls == 1 ? 256 : 128); }
+// the re-base threshold of the general kernels (VISTA_ATTN_RESCALE_THR: tuning / A-B)
+static float attn_rescale_thr() {
+    static const float thr = [] { const char* e = getenv("VISTA_ATTN_RESCALE_THR"); return e ? (float)atof(e) : RESCALE_THR; }();
+    return thr;
+}
 
 extern "C" int vk_attn_spatial_fp8qk(const void* q8, const void* k8, const void* q_scales, const void* k_scales, const void* v, void* o, void* o8,
                                      void* o_scales, int32_t n_img, int32_t heads, int32_t S, int32_t ldq8, int32_t ldk8, int32_t ldqs, int32_t ldks,
@@ -1204,9 +1113,9 @@ extern "C" int vk_attn_spatial_fp8qk(const void* q8, const void* k8, const void*
     if (!q8 || !k8 || !q_scales || !k_scales || !v || (!o && !o8) || (o8 && !o_scales) || n_img <= 0 || heads <= 0 || S <= 0) return VK_EINVAL;
     if ((S % 8) != 0 || (ldq8 % 16) != 0 || (ldk8 % 16) != 0 || (ldv % 8) != 0 || (o && (ldo % 4) != 0) || (o8 && (ldo8 % 16) != 0)) return VK_EINVAL;
     if ((((size_t)q8) & 15) || (((size_t)k8) & 15) || (o8 && (((size_t)o8) & 15))) return VK_EINVAL;
-    static const float thr = [] { const char* e = getenv("VISTA_ATTN_RESCALE_THR"); return e ? (float)atof(e) : RESCALE_THR; }();
-    const int cls = S >= 4096 ? 2 : (S >= 2048 ? 1 : 0);
-    const int qb_rows = cls == 2 ? 512 : (cls == 1 ? 256 : 128);
+    const float thr = attn_rescale_thr();
+    const int cls = attn_seq_class(S);
+    const int qb_rows = attn_class_rows(cls);
     const long long nblk = (long long)((S + qb_rows - 1) / qb_rows) * n_img * heads;
     if (nblk > 0x7fffffffLL) return VK_EINVAL;
     const bool pre = scale == 0.f;  // scale == 0: the query already carries softmax_scale * log2(e) (see vk_attn_spatial_qkv_log2_bf16)
@@ -1319,12 +1228,8 @@ static int attn_spatial_launch(const void* q, const void* k, const void* vt, voi
     if ((S % 8) != 0 || (ldq % 8) != 0 || (ldk % 8) != 0 || (ldo % 4) != 0) return VK_EINVAL;
     // operand contract (include/vista_hip.h): q / k / v (or V^T) arrive in 16-byte pieces; the general kernels store 8 bytes of o at a time
     if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(vt, 16) || !aligned_to(o, 8)) return VK_EINVAL;
-    // long sequences: 256 query rows (8 waves) per workgroup halve the K/V^T stream per FLOP; short ones keep 128 rows so the
-    // ragged last q-block wastes less (S = 144, 576 at the deep levels)
-    static const float thr = [] { const char* e = getenv("VISTA_ATTN_RESCALE_THR"); return e ? (float)atof(e) : RESCALE_THR; }();  // tuning / A-B
-    // long sequences: 8 waves x 64 query rows (512 per workgroup): every K / V^T fragment read feeds two MFMAs and the K/V^T stream
-    // per FLOP halves again; medium ones 8 x 32; short ones 4 x 32 so the ragged last q-block wastes less (S = 144, 576 at the deep levels)
-    int cls = S >= 4096 ? 2 : (S >= 2048 ? 1 : 0);
+    const float thr = attn_rescale_thr();
+    int cls = attn_seq_class(S);
     if (cls == 2) {
         // few images (one rank of a frame-sharded run): the 512-row workgroups run ONE per CU, so e.g. 7 images x 5 heads x 18 blocks = 630 of
         // them are 2.46 rounds = 3; 256-row workgroups (two per CU) finish the same work 8.5 % sooner (0.88 -> 0.805 ms), while at 8 / 13 / 50
@@ -1333,7 +1238,7 @@ static int attn_spatial_launch(const void* q, const void* k, const void* vt, voi
         const long long rounds = (n2 + 255) / 256;
         if (n2 * 100 < rounds * 256 * 85) cls = 1;
     }
-    const int qb_rows = cls == 2 ? 512 : (cls == 1 ? 256 : 128);
+    const int qb_rows = attn_class_rows(cls);
     const int nqb = (S + qb_rows - 1) / qb_rows;
     const long long nblk = (long long)nqb * n_img * heads;
     if (nblk > 0x7fffffffLL) return VK_EINVAL;

@@ -85,6 +85,58 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---- lane-pair helpers of the 32x32 MFMA accumulator layout (GEMM epilogues, attention output stores) ----
+// Accumulator element r = 4*g + e: lane l31 of the lower half-wave (lh = 0) holds columns c..c+3 of accumulator quad g and lane l31 of the
+// upper half the next four, for the SAME output row. Swapping the upper half of quad g with the lower half of quad g+1 (v_permlane32_swap)
+// leaves the lower lane with 8 contiguous bf16 of quad g and the upper lane with 8 contiguous bf16 of quad g+1: one 16-byte store instead
+// of two 8-byte ones. The epilogue of the GEMMs is store-ISSUE bound (16-40 stores per lane), so halving the count matters most
+// where tiles are short (K = 320: 5 K-steps per tile).
+__device__ __forceinline__ uint4 widen_pair(uint2 qa, uint2 qb) {
+    const auto rx = __builtin_amdgcn_permlane32_swap(qa.x, qb.x, false, false);
+    const auto ry = __builtin_amdgcn_permlane32_swap(qa.y, qb.y, false, false);
+    return make_uint4(rx[0], ry[0], rx[1], ry[1]);
+}
+
+// The inverse, for loads: the lower lane read the 8 contiguous bf16 of quad g (its own 4 and its partner's 4), the upper lane those of
+// quad g+1; two swaps hand every lane its own 4 values of both quads.
+__device__ __forceinline__ void unwiden_pair(const uint4& w, uint2& qa, uint2& qb) {
+    const auto rx = __builtin_amdgcn_permlane32_swap(w.x, w.z, false, false);
+    const auto ry = __builtin_amdgcn_permlane32_swap(w.y, w.w, false, false);
+    qa = make_uint2(rx[0], ry[0]);
+    qb = make_uint2(rx[1], ry[1]);
+}
+
+__device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float d) {
+    int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
+    return (uint32_t)v;
+}
+
+// MX-fp8 quantisation of ONE 32-column block of an output row held as the four accumulator quads of a 32x32 fragment: lane half lh holds
+// columns 8g + 4lh + e (g = quad, e = 0..3), i.e. 16 of the 32 values; its partner lane (l ^ 32) the others. Returns the lane's 16 bytes
+// of the block's 32 e4m3 bytes (to be stored at byte offset 16*lh of the block) and the block's E8M0 exponent byte (both lanes get it):
+// 2^(ex) >= max|v| / 448, the smallest such power of two (frexp), so every value lands in e4m3's range with at most one binade unused.
+__device__ __forceinline__ uint4 mx_quant_block(const float (&v)[4][4], int& e8m0) {
+    float amax = 0.f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fabsf(v[g][e]));
+    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+    int ex = -127;
+    if (amax > 0.f) frexpf(amax * (1.f / 448.f), &ex);  // amax/448 = f * 2^ex, f in [0.5, 1)
+    ex = ex < -127 ? -127 : (ex > 127 ? 127 : ex);
+    const float inv = ldexpf(1.f, -ex);
+    uint32_t q[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) q[g] = pack_fp8x4(v[g][0] * inv, v[g][1] * inv, v[g][2] * inv, v[g][3] * inv);
+    // lower lane: [own q0 | partner q0 | own q1 | partner q1] = columns 0-15; upper lane: [partner q2 | own q2 | partner q3 | own q3] = 16-31
+    const auto r02 = __builtin_amdgcn_permlane32_swap(q[0], q[2], false, false);
+    const auto r13 = __builtin_amdgcn_permlane32_swap(q[1], q[3], false, false);
+    e8m0 = ex + 127;
+    return make_uint4(r02[0], r02[1], r13[0], r13[1]);
+}
+
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 // erf-form GELU (F.gelu default, reference vwm/modules/attention.py:92): x * Phi(x) with the normal CDF as a logistic of an odd quintic,
 // Phi(x) ~= 1 / (1 + exp(-x (a + b x^2 + c x^4))), a = 1.59501577, b = 7.40112920e-2, c = -7.03033577e-4 (minimax fit of x * Phi(x) over
