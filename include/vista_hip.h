@@ -718,6 +718,54 @@ int vk_jpeg_interval_sizes(const void* coef, int32_t* sizes, int32_t n, int32_t 
 int vk_jpeg_entropy_write(const void* coef, const int64_t* offsets, void* out, int64_t out_bytes, int32_t n, int32_t mcu_h, int32_t mcu_w,
                           int32_t blocks, void* stream);
 
+/* ------------------------------------------------------------------ PNG output (csrc/png.hip)
+ * Added under ABI v9 without a version step, as the Motion-JPEG entry points were: purely additive. uint8 in, bytes out, integer arithmetic only,
+ * storage-type independent: the same code is linked into both libraries. The PNG signature and chunks, the two-byte zlib header, the combination
+ * of the segments' Adler-32 pairs into a frame's checksum and the chunk CRCs are the host's (vista_amd/png.py).
+ *
+ * vk_png_filter_u8: frames (n, H, W, 3) uint8 -> rows (n, H, 1 + 3 W) uint8: per row the filter type and the filtered bytes. All five types are
+ * coded (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth; bpp = 3; the row above a frame's first row is zero: each frame is independent) and the type
+ * with the smallest sum of the bytes' absolute values, read as signed, is kept (libpng's heuristic); on a tie the lowest type.
+ *   Operands: frames and rows dense, any alignment (byte accesses). n >= 1, 1 <= H, W <= VK_PNG_MAX_EXTENT, n H (1 + 3 W) at most 2^31 - 1.
+ *   VK_EINVAL, before any HIP call: a NULL pointer, an extent outside those limits.
+ *
+ * vk_png_deflate_plan / vk_png_deflate_write: rows (n, H, row_bytes) uint8 -- any row_bytes, not only 1 + 3 W -- are cut into segments of seg_rows
+ * rows (a frame's last may be shorter); segment i of the call is segment i % segs of frame i / segs, segs = ceil(H / seg_rows). A segment is coded
+ * as exactly ONE dynamic-Huffman deflate block (BTYPE 10), BFINAL set only on a frame's last segment; every other segment is followed by an
+ * empty stored block (BFINAL 0, BTYPE 00, zero bits to the byte, 00 00 FF FF), so every segment starts on a byte boundary and a frame's
+ * segments, back to back, are one raw deflate stream.
+ *   Tokens (zlib's Z_RLE, restated): at position i >= 1 of the segment, if bytes i, i + 1 and i + 2 equal byte i - 1, a match of distance 1 and
+ *   length min(rest of the run inside the segment, 258); otherwise a literal. Nothing refers behind the segment's start; runs cross rows.
+ *   Codes: a pure function of the segment's histogram. Fewer than two used symbols: symbols 0, then 1, are counted once until two are. The used
+ *   symbols sorted by (count, symbol) ascending are the leaves of a two-queue Huffman construction (leaves in that order, internal nodes in order
+ *   of creation; the lighter front is taken, the leaf on a tie); a length is a leaf's depth. While the longest length exceeds the limit (15 for
+ *   literal/length, 7 for the code-length alphabet) every used count becomes (count + 1) >> 1 and the construction is repeated. The distance
+ *   alphabet is distance 1 alone: one code of length 1 where the segment holds a match, a single zero length where it holds none. Canonical codes
+ *   (RFC 1951 3.2.2). Tree description: the literal/length lengths up to the last used symbol (at least 257), then the one distance length
+ *   (HDIST 0); a run of r zeros is 18 (11 .. 138) while r >= 11, then 17 if r >= 3, else r times 0; a run of r equal lengths v > 0 is v, then 16
+ *   (3 .. 6) while at least 3 remain, then v for each left; runs end with the literal/length lengths.
+ * vk_png_deflate_plan writes, per segment: sizes[i] int32, its bytes (stored block included); adler[2 i], adler[2 i + 1], the Adler-32 sums
+ * (s1, s2) of the segment's bytes alone, started from 1; plan[i * VK_PNG_PLAN_WORDS ...] uint32: word 0 the bits of the block header and tree
+ * description, word 1 the distance code's length, words 4 .. 289 per literal/length symbol (bit-reversed code | length << 16), words 290 .. 419
+ * the header's bits, LSB first. The trees are built on the GPU: between the two calls only the sizes travel.
+ * vk_png_deflate_write writes segment i at out + offsets[i] (int64, DEVICE memory; the caller's exclusive sum of the sizes). Every byte of
+ * [offsets[i], offsets[i] + sizes[i]) is stored exactly once by a plain store and no other byte is touched: out need not be zeroed. A byte that
+ * would fall outside [0, out_bytes) is not stored. A workgroup per segment streams through it 256 bytes at a time: a segment need not fit LDS.
+ *   segments  the segment count, stated by the caller: it must equal n * ceil(H / seg_rows).
+ *   Operands: rows dense, any alignment; sizes, adler and plan 4-byte, offsets 8-byte aligned; out any alignment.
+ *   n, H, row_bytes, seg_rows >= 1; n H row_bytes at most 2^31 - 1; a segment, min(seg_rows, H) * row_bytes, at most VK_PNG_MAX_SEGMENT_BYTES
+ *   (2^24: the grid of 91 frames of 576 x 1024, 6360 rows of 27709 bytes, has segments of 443344); 1 <= out_bytes <= 2^31 - 1.
+ *   VK_EINVAL, before any HIP call: a NULL pointer, an extent outside those limits, segments != n * ceil(H / seg_rows), a misaligned sizes /
+ *   adler / plan / offsets. */
+#define VK_PNG_MAX_EXTENT 65535
+#define VK_PNG_MAX_SEGMENT_BYTES (1 << 24)
+#define VK_PNG_PLAN_WORDS 420
+int vk_png_filter_u8(const void* frames, void* rows, int32_t n, int32_t H, int32_t W, void* stream);
+int vk_png_deflate_plan(const void* rows, int32_t* sizes, uint32_t* adler, uint32_t* plan, int32_t n, int32_t H, int32_t row_bytes, int32_t seg_rows,
+                        int32_t segments, void* stream);
+int vk_png_deflate_write(const void* rows, const uint32_t* plan, const int64_t* offsets, void* out, int64_t out_bytes, int32_t n, int32_t H,
+                         int32_t row_bytes, int32_t seg_rows, int32_t segments, void* stream);
+
 /* library info */
 int vk_abi_version(void);
 /* ABI v7: the 16-bit storage type this library was built for: 0 = bf16 (libvista_hip.so, the default and the BASELINE config's dtype), 1 = IEEE fp16

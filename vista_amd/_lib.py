@@ -163,6 +163,9 @@ SIGNATURES = {
     "vk_jpeg_dct_quant_u8": [_vp, _vp, C.POINTER(VkJpegQuant), _i32, _i32, _i32, _vp],
     "vk_jpeg_interval_sizes": [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "vk_jpeg_entropy_write": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
+    "vk_png_filter_u8": [_vp, _vp, _i32, _i32, _i32, _vp],
+    "vk_png_deflate_plan": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "vk_png_deflate_write": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp],
     "vk_abi_version": [],
     "vk_act_dtype": [],
 }

@@ -338,6 +338,7 @@ def plan_run(opt, argv=None, net_params=None):
     SU.check_sizes(opt.height, opt.width, opt.n_frames, len(entries), opt.n_conds, net_params)
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
+    SU.png_format()     # (and a bad VISTA_PNG)
     return entries
 
 

@@ -47,6 +47,7 @@ def check_run(opt, net_params=None):
     SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, net_params)
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
+    SU.png_format()     # (and a bad VISTA_PNG)
     if opt.height < fidelity.TAPS or opt.width < fidelity.TAPS:
         raise ValueError(f"--height {opt.height} --width {opt.width}: SSIM takes an {fidelity.TAPS} x {fidelity.TAPS} window")
     if opt.dataset == "IMG":

@@ -1886,3 +1886,57 @@ def jpeg_entropy(coef, mcu_h, mcu_w):
     scan = torch.empty(total, dtype=torch.uint8, device=coef.device)
     check(lib.vk_jpeg_entropy_write(_p(coef), _p(offsets), _p(scan), total, n, mcu_h, mcu_w, n * blocks, _stream()), "vk_jpeg_entropy_write")
     return scan, host
+
+
+# ---- PNG output (csrc/png.hip) ----
+PNG_MAX_EXTENT, PNG_MAX_SEGMENT_BYTES, PNG_PLAN_WORDS = 65535, 1 << 24, 420   # the limits include/vista_hip.h states beside the three prototypes
+
+
+def png_filter(frames):
+    """frames (n, H, W, 3) uint8, dense, on the GPU -> rows (n, H, 1 + 3 W) uint8: per row the PNG filter type libpng's heuristic picks (the smallest
+    sum of |byte as int8| over None, Sub, Up, Average, Paeth; the lowest type on a tie) and the filtered bytes (vk_png_filter_u8). Nothing is
+    synchronised."""
+    _jpeg_operand(frames, "frames", torch.uint8, 4, 3, 1)
+    n, H, W, _ = frames.shape
+    if not (n >= 1 and 1 <= H <= PNG_MAX_EXTENT and 1 <= W <= PNG_MAX_EXTENT):
+        raise OperandError(f"frames: n >= 1 and 1 <= H, W <= {PNG_MAX_EXTENT}, got {tuple(frames.shape)}")
+    if n * H * (1 + 3 * W) > JPEG_MAX_COUNT:
+        raise OperandError(f"frames: {tuple(frames.shape)} gives {n * H * (1 + 3 * W)} bytes of rows; they must stay below 2^31 (encode fewer frames "
+                           "per call)")
+    rows = torch.empty((n, H, 1 + 3 * W), dtype=torch.uint8, device=frames.device)
+    check(_lib.load().vk_png_filter_u8(_p(frames), _p(rows), n, H, W, _stream()), "vk_png_filter_u8")
+    return rows
+
+
+def png_deflate(rows, seg_rows=16):
+    """rows (n, H, row_bytes) uint8, dense, on the GPU (any row_bytes) -> (stream, offsets, adler): `stream` a uint8 GPU tensor that holds every
+    frame's raw deflate data back to back, one dynamic-Huffman block per segment of `seg_rows` rows; `offsets` the n * segs + 1 exclusive byte
+    offsets of the segments as a CPU int64 tensor (segs = ceil(H / seg_rows); frame i is stream[offsets[i * segs] : offsets[(i + 1) * segs]]);
+    `adler` (n * segs, 2) int64 on the CPU, the Adler-32 sums (s1, s2) of each segment's bytes alone. vk_png_deflate_plan builds the trees on the
+    GPU; a cumulative sum and ONE transfer of the offsets to the host (the only synchronisation between the kernels: the output's size is data);
+    vk_png_deflate_write."""
+    _jpeg_operand(rows, "rows", torch.uint8, 3, rows.shape[-1] if torch.is_tensor(rows) and rows.dim() else 0, 1)
+    if isinstance(seg_rows, bool) or not isinstance(seg_rows, int) or not 1 <= seg_rows <= JPEG_MAX_COUNT:
+        raise OperandError(f"seg_rows: a whole number of rows per segment, at least 1, got {seg_rows!r}")
+    n, H, row_bytes = rows.shape
+    if n < 1 or H < 1 or row_bytes < 1 or n * H * row_bytes > JPEG_MAX_COUNT:
+        raise OperandError(f"rows: {tuple(rows.shape)} must hold n, H, row_bytes >= 1 and at most 2^31 - 1 bytes (encode fewer frames per call)")
+    if min(seg_rows, H) * row_bytes > PNG_MAX_SEGMENT_BYTES:
+        raise OperandError(f"rows: a segment of {min(seg_rows, H)} rows of {row_bytes} bytes is {min(seg_rows, H) * row_bytes} bytes; at most "
+                           f"{PNG_MAX_SEGMENT_BYTES} (lower seg_rows)")
+    segs = (H + seg_rows - 1) // seg_rows
+    lib, dev = _lib.load(), rows.device
+    sizes = torch.empty(n * segs, dtype=torch.int32, device=dev)
+    adler = torch.empty((n * segs, 2), dtype=torch.int32, device=dev)
+    plan = torch.empty((n * segs, PNG_PLAN_WORDS), dtype=torch.int32, device=dev)
+    check(lib.vk_png_deflate_plan(_p(rows), _p(sizes), _p(adler), _p(plan), n, H, row_bytes, seg_rows, n * segs, _stream()), "vk_png_deflate_plan")
+    offsets = torch.zeros(n * segs + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(sizes, 0, dtype=torch.int64)
+    host = offsets.cpu()
+    total = int(host[-1])
+    if not 1 <= total <= JPEG_MAX_COUNT:
+        raise OperandError(f"rows: the streams take {total} bytes; the output must stay below 2^31 (encode fewer frames per call)")
+    stream = torch.empty(total, dtype=torch.uint8, device=dev)
+    check(lib.vk_png_deflate_write(_p(rows), _p(plan), _p(offsets), _p(stream), total, n, H, row_bytes, seg_rows, n * segs, _stream()),
+          "vk_png_deflate_write")
+    return stream, host, adler.cpu().to(torch.int64)

@@ -6,7 +6,7 @@ Same names, arguments and defaults as the reference. Differences, all stated whe
 on the GPU (ops.load_img_batch, Pillow's LANCZOS byte for byte), frames are converted to 8 bit on the GPU (ops.frames_to_u8), nothing is
 shuffled between host and device (`--low_vram` is a no-op: 288 GB of HBM keep every stage resident), and without `imageio` a video is written as
 an animated PNG instead of an mp4 (or, with VISTA_VIDEO=mjpeg, as Motion-JPEG in AVI whose frames are encoded on the GPU: video_format, README
-"Videos").
+"Videos"). With VISTA_PNG=hip every PNG stream -- images, grids, the animated PNG -- is filtered and deflated on the GPU (png_format, README "Pictures").
 """
 import json
 import math
@@ -75,6 +75,19 @@ def video_format():
     if not 1 <= quality <= 100:
         raise ValueError(f"Bad JPEG quality {text} (environment hook VISTA_VIDEO_QUALITY): a whole number from 1 to 100")
     return name, quality
+
+
+PNG_FORMATS = ("pillow", "hip")
+
+
+def png_format():
+    """-> how the package codes the PNG streams it writes. The one place the environment hook VISTA_PNG is read. Unset or `pillow`: Pillow on the
+    host, every file byte for byte what was written before the hook existed. `hip`: the rows are filtered and deflated on the GPU (png.py,
+    csrc/png.hip) -- the per-frame images, the grids and the animated PNG. An unknown value is refused here, by name, before a model is built."""
+    name = os.environ.get("VISTA_PNG") or "pillow"
+    if name not in PNG_FORMATS:
+        raise ValueError(f"Unknown PNG coder {name} (environment hook VISTA_PNG): one of {', '.join(PNG_FORMATS)}")
+    return name
 
 
 def get_sampler(sampler, steps, discretization_config, guider_config):
@@ -291,18 +304,22 @@ def _to_u8(samples, real, grid=False):
 def save_video(path_stem, frames_u8, fps=10):
     """(t, H, W, 3) uint8 -> `<stem>.mp4` through imageio where it is importable (the reference's writer); otherwise `<stem>.apng`, an animated
     PNG at 1000 / fps ms per frame (lossless, so the frames read back exactly). With VISTA_VIDEO=mjpeg (video_format): `<stem>.avi`, Motion-JPEG;
-    the frames may then be a uint8 GPU tensor, which is encoded where it lies, or numpy, which is uploaded. Returns the path written."""
+    the frames may then be a uint8 GPU tensor, which is encoded where it lies, or numpy, which is uploaded. With VISTA_PNG=hip (png_format) the
+    `.apng` is written by png.write_apng, its streams coded on the GPU, from a GPU tensor or numpy alike. Returns the path written."""
     fmt, quality = video_format()
     if fmt == "mjpeg":
         from . import video
         H, W = int(frames_u8.shape[1]), int(frames_u8.shape[2])
         return video.write_avi(path_stem + ".avi", video.encode_jpeg(frames_u8, quality), W, H, fps)
-    if torch.is_tensor(frames_u8):
-        frames_u8 = frames_u8.cpu().numpy()
     try:
         import imageio
     except ImportError:
         imageio = None
+    if imageio is None and png_format() == "hip":
+        from . import png
+        return png.write_apng(path_stem + ".apng", frames_u8, fps)
+    if torch.is_tensor(frames_u8):
+        frames_u8 = frames_u8.cpu().numpy()
     if imageio is not None:
         path = path_stem + ".mp4"
         writer = imageio.get_writer(path, fps=fps)
@@ -341,7 +358,8 @@ def perform_save_locally(save_path, samples, mode, dataset_name, sample_index):
     `<dataset>_<index:06>.png`, videos `<dataset>_<index:06>.mp4` at 10 fps. A save_path containing "real" holds inputs in [-1, 1], any other
     samples in [0, 1]. The 8-bit conversion (and the make_grid layout) runs in vk_frames_to_u8. Deviation: without imageio the video is an
     animated PNG (`.apng`, 100 ms per frame) instead of an mp4; with VISTA_VIDEO=mjpeg it is `<stem>.avi` (README "Videos"), and the 8-bit frames
-    go from vk_frames_to_u8 to the JPEG kernels without leaving the GPU."""
+    go from vk_frames_to_u8 to the JPEG kernels without leaving the GPU. With VISTA_PNG=hip (README "Pictures") the images, the grid and the
+    animated PNG are coded on the GPU (png.encode_png / png.write_apng) under the same file names: the 8-bit frames never make the host round trip."""
     from PIL import Image
     if mode not in ("images", "grids", "videos"):
         raise AssertionError(mode)
@@ -349,12 +367,18 @@ def perform_save_locally(save_path, samples, mode, dataset_name, sample_index):
     os.makedirs(merged_path, exist_ok=True)
     real = "real" in save_path
     stem = os.path.join(merged_path, f"{dataset_name}_{sample_index:06}")
-    if mode == "images":
+    if png_format() == "hip" and mode != "videos":
+        from . import png
+        names = [f"{stem}_{count:04}.png" for count in range(samples.shape[0])] if mode == "images" else [stem + ".png"]
+        for name, data in zip(names, png.encode_png(ops.frames_to_u8(samples.float(), real=real, grid=mode == "grids"))):
+            with open(name, "wb") as f:
+                f.write(data)
+    elif mode == "images":
         for count, frame in enumerate(_to_u8(samples, real)):
             Image.fromarray(frame).save(f"{stem}_{count:04}.png")
     elif mode == "grids":
         Image.fromarray(_to_u8(samples, real, grid=True)).save(stem + ".png")
-    elif video_format()[0] == "mjpeg":
+    elif video_format()[0] == "mjpeg" or png_format() == "hip":
         save_video(stem, ops.frames_to_u8(samples.float(), real=real), 10)
     else:
         save_video(stem, _to_u8(samples, real), 10)

@@ -190,6 +190,7 @@ def main(argv=None):
     SU.check_sizes(opt.height, opt.width, opt.n_frames, 1, opt.n_conds, frontdoor.net_params(opt))
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
+    SU.png_format()     # (and a bad VISTA_PNG)
     if opt.ens_size < 2:
         raise ValueError(f"--ens_size {opt.ens_size}: reward estimation needs at least two ensemble members (unbiased variance)")
     if opt.heat_max is not None and not opt.heat_max > 0.0:

@@ -159,6 +159,7 @@ def main(argv=None):
     SU.check_sizes(opt.height, opt.width, opt.n_frames, opt.n_rounds, opt.n_conds, frontdoor.net_params(opt))
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
+    SU.png_format()     # (and a bad VISTA_PNG)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:   # one rank of a torch.distributed.run job
         rank, shard = init_distributed(opt.n_frames)
         try:
