@@ -522,7 +522,7 @@ int vk_heat_overlay_u8(const float* frames, const float* map, void* out, int32_t
  *                  partials in a fixed order. Which workgroup owns what is a function of (H, W) alone: no atomics, bitwise repeatable, and a
  *                  frame's values do not change with n or with the frames around it.
  *   Where W % 4 == 0 the halo is loaded 4 bytes per lane: a and b must then be 4-byte aligned; any other W takes any alignment.
- *   The entry point allocates nothing and synchronises nothing. Not built here: any perceptual metric that needs a pretrained network.
+ *   The entry point allocates nothing and synchronises nothing.
  *   VK_EINVAL: a NULL pointer, n <= 0, n > 65535, H < 11 or W < 11, ws / sse / ssim_sum not 8-byte aligned, a or b misaligned where W % 4 == 0,
  *   a frame of more tiles than vk_frame_fidelity_ws_bytes can state.
  * vk_frame_fidelity_ws_bytes: the workspace bytes PER FRAME for (H, W) frames, or VK_EINVAL (H < 11, W < 11, more than 2^31 - 1 bytes). */
@@ -532,6 +532,47 @@ int vk_heat_overlay_u8(const float* frames, const float* map, void* out, int32_t
 int vk_frame_fidelity_ws_bytes(int32_t H, int32_t W);
 int vk_frame_fidelity_u8(const void* a, const void* b, uint64_t* sse, double* ssim_sum, void* ws, const float* window11 /* HOST memory */,
                          int32_t n, int32_t H, int32_t W, void* stream);
+
+/* ------------------------------------------------------------------ CLIP-space scores (csrc/perceptual.hip)
+ * Added under ABI v9 without a version step: purely additive, so vk_abi_version() stays 9. No float atomics: two calls on the same input return
+ * the same bits. The entry points allocate nothing and synchronise nothing. Only the 16-bit store of the first one sees the storage type.
+ *
+ * vk_clip_preprocess_patches_u8: vk_clip_preprocess_patches (declared with the conditioner's entries) for `img` (n_img, H, W, 3) uint8, dense: the bytes
+ * vk_frames_to_u8 writes and the saved pictures hold. A byte b stands for (float)b / 127.5f - 1.0f (one fp32 division, one fp32 subtraction,
+ * not contracted); from there the arithmetic is the fp32 entry's, operation for operation (csrc/clip_resample.h), so `out` equals, bit for bit,
+ * what vk_clip_preprocess_patches of the same library writes for the frames converted that way. Every other argument as there; the caller
+ * zero-fills `out`. A workgroup stages the source rectangle of a tile of outputs into LDS as fp32; the tile is the largest of 16, 8, 4, 2, 1
+ * outputs a side whose rectangle fits 60 KiB. Where W % 4 == 0 and img is 4-byte aligned the rectangle is loaded 4 bytes per lane, else a
+ * byte per lane: any W and any base address are taken.
+ *   VK_EINVAL: what vk_clip_preprocess_patches refuses; n_img > 65535; out_hw > 4096; H or W > VK_CLIP_U8_MAX_SIDE; a blur radius ks / 2 that
+ *   is not smaller than the side it runs along; `out` not 2-byte aligned.
+ *
+ * vk_embed_row_stats: a, b (n, d) fp32, dense -> out (n, 3) fp64: per row a.b, a.a, b.b. fp32 values multiplied (exactly) and summed in
+ * fp64; the order of the three sums is one function of d, so a == b gives three equal bit patterns and a cosine of exactly 1.
+ *   VK_EINVAL: a NULL pointer, n or d <= 0, n > VK_EMBED_MAX_ROWS, d > VK_EMBED_MAX_DIM, a / b not 4-byte or out not 8-byte aligned.
+ *
+ * vk_embed_mmd_sums: x (m, d), y (n, d) fp32, dense -> out3, 3 fp64: with u^ = u times the fp32 inverse of its norm (the norm from the fp64
+ * sum of squares) and k(u, v) = exp(-|u - v|^2 / (2 sigma^2)),
+ *   out3[0] = sum over i < j of 1 - k(x^_i, x^_j),   out3[1] = likewise over y,   out3[2] = sum over all (i, j) of 1 - k(x^_i, y^_j).
+ * Per pair |u - v|^2 is the fp32 sum over the columns, in ascending order, of the squared fp32 differences (an FMA of the difference with
+ * itself into the sum; never 2 - 2 u.v), and 1 - k is -expm1f(-gamma * that), gamma = (float)(1 / (2 sigma^2)); the terms are added in fp64:
+ * per workgroup (a VK_EMBED_MMD_TILE^2 block of pairs) in a fixed order into the workspace, then folded in a fixed order. Two equal rows
+ * contribute exactly 0. m == 1 gives out3[0] == 0. A row whose norm is zero or not finite makes every sum it is in NaN; nothing faults.
+ *   ws: vk_embed_mmd_ws_bytes(m, n, d) bytes of scratch, the caller's, 8-byte aligned.
+ *   VK_EINVAL: a NULL pointer, m / n / d < 1, m or n > VK_EMBED_MAX_ROWS, d > VK_EMBED_MAX_DIM, sigma not positive and finite, x / y not
+ *   4-byte or out3 / ws not 8-byte aligned.
+ * vk_embed_mmd_ws_bytes: the workspace bytes, 24 per tile of pairs of the larger set with itself plus 4 per row, or VK_EINVAL: a shape
+ * vk_embed_mmd_sums refuses, or more than 2^31 - 1 bytes (sets beyond about 600,000 rows), which vk_embed_mmd_sums then refuses too. */
+#define VK_CLIP_U8_MAX_SIDE 65536
+#define VK_EMBED_MAX_ROWS (1 << 20)
+#define VK_EMBED_MAX_DIM (1 << 16)
+#define VK_EMBED_MMD_TILE 64
+int vk_clip_preprocess_patches_u8(const void* img, void* out, int32_t n_img, int32_t H, int32_t W, int32_t out_hw, int32_t patch, int32_t ldo,
+                                  float sigma_y, float sigma_x, int32_t ks_y, int32_t ks_x, const float* mean3 /* HOST memory */,
+                                  const float* std3 /* HOST memory */, void* stream);
+int vk_embed_row_stats(const float* a, const float* b, double* out, int32_t n, int32_t d, void* stream);
+int vk_embed_mmd_ws_bytes(int32_t m, int32_t n, int32_t d);
+int vk_embed_mmd_sums(const float* x, const float* y, double* out3, void* ws, int32_t m, int32_t n, int32_t d, float sigma, void* stream);
 
 /* ------------------------------------------------------------------ exchange packing of the frame-sharded step (ABI v9; csrc/reshard.hip)
  * Storage-type independent: the same code is linked into both libraries.

@@ -1,6 +1,7 @@
 // Small HBM-bound elementwise / layout kernels around the UNet and the EulerEDM sampler step (gfx950).
 // Reference call sites are listed per entry point in include/vista_hip.h.
 #include "common.h"
+#include "clip_resample.h"
 #include "vista_hip.h"
 
 namespace {
@@ -266,66 +267,29 @@ __global__ void ens_var_final_kernel(const double* __restrict__ partial, double*
 
 
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int CLIP_MAX_KS = 63;  // largest odd Gaussian kernel of the antialias blur (a side of ~7000 px resized to 224)
 // OpenCLIP image preprocessing + patchify in one pass (FrozenOpenCLIPImageEmbedder.preprocess, vwm/modules/encoders/modules.py:304-315,
-// then the 14x14 / stride-14 patch convolution's im2col): kornia 0.6.9 `resize(x, (224, 224), "bicubic", align_corners=True, antialias=True)`
-// = separable Gaussian blur (reflect border; sigma = (factor - 1) / 2 per axis, kernel size int(max(4 sigma, 3)) made odd -- only when
-// downscaling) followed by F.interpolate(mode="bicubic", align_corners=True) (A = -0.75, clamped taps); then (x + 1) / 2 and the CLIP
-// mean / std. One thread per output pixel; its value is written straight into the patch-embedding GEMM's A operand:
+// then the 14x14 / stride-14 patch convolution's im2col). The resize and the normalisation are clip_resample.h's, shared with the kernel
+// that reads 8-bit frames (perceptual.hip). One thread per output pixel; its value is written straight into the patch-embedding GEMM's A
+// operand:
 //   out[(img * (1 + gp*gp) + 1 + py*gp + px)][c*ps*ps + ky*ps + kx]   bf16, row stride ldo (columns 3*ps*ps .. ldo-1 zero), row 0 of each
 //   image (the class-token slot) zero.
-__device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
-__device__ __forceinline__ int reflect_idx(int i, int n) { i = i < 0 ? -i : i; return i >= n ? 2 * (n - 1) - i : i; }
-
 __global__ __launch_bounds__(EW_THREADS) void clip_preprocess_kernel(const float* __restrict__ img, uint16_t* __restrict__ out, int n_img, int H, int W,
                                                                      int out_hw, int ps, int ldo, float sig_y, float sig_x, int ks_y, int ks_x,
                                                                      float m0, float m1, float m2, float s0, float s1, float s2) {
     const int gp = out_hw / ps;
     const long long total = (long long)n_img * 3 * out_hw * out_hw;
-    // Gaussian taps (the same for every output value): once per workgroup, in LDS, in the order and arithmetic of the per-thread form they
-    // replace (a runtime-indexed register array lives in scratch: 2 x 63 floats per lane); ks == 1 = no blur along that axis
     __shared__ float gy[CLIP_MAX_KS], gx[CLIP_MAX_KS];
-    if ((int)threadIdx.x < ks_y) { const float d = (float)((int)threadIdx.x - ks_y / 2); gy[threadIdx.x] = ks_y > 1 ? expf(-d * d / (2.f * sig_y * sig_y)) : 1.f; }
-    if ((int)threadIdx.x < ks_x) { const float d = (float)((int)threadIdx.x - ks_x / 2); gx[threadIdx.x] = ks_x > 1 ? expf(-d * d / (2.f * sig_x * sig_x)) : 1.f; }
-    __syncthreads();
-    float ny = 0.f, nx = 0.f;
-    for (int k = 0; k < ks_y; ++k) ny += gy[k];
-    for (int k = 0; k < ks_x; ++k) nx += gx[k];
+    float ny, nx;
+    clip_gauss_taps(gy, gx, ks_y, ks_x, sig_y, sig_x, ny, nx);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int ox = (int)(i % out_hw);
         const int oy = (int)((i / out_hw) % out_hw);
         const int c = (int)((i / ((long long)out_hw * out_hw)) % 3);
         const int n = (int)(i / ((long long)3 * out_hw * out_hw));
         const float* src = img + ((size_t)n * 3 + c) * H * W;
-        const float ry = out_hw > 1 ? (float)oy * ((float)(H - 1) / (float)(out_hw - 1)) : 0.f;
-        const float rx = out_hw > 1 ? (float)ox * ((float)(W - 1) / (float)(out_hw - 1)) : 0.f;
-        const int iy = (int)floorf(ry), ix = (int)floorf(rx);
-        const float ty = ry - (float)iy, tx = rx - (float)ix;
-        const float A = -0.75f;
-        const float wy[4] = {cubic2(ty + 1.f, A), cubic1(ty, A), cubic1(1.f - ty, A), cubic2(2.f - ty, A)};
-        const float wx[4] = {cubic2(tx + 1.f, A), cubic1(tx, A), cubic1(1.f - tx, A), cubic2(2.f - tx, A)};
-        float acc = 0.f;
-        for (int a = 0; a < 4; ++a) {
-            int yy = iy - 1 + a;
-            yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);  // bicubic taps are clamped to the (blurred) image
-            float rowacc = 0.f;
-            for (int b = 0; b < 4; ++b) {
-                int xx = ix - 1 + b;
-                xx = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx);
-                float v = 0.f;  // blurred(yy, xx): reflect-padded separable Gaussian
-                for (int ky = 0; ky < ks_y; ++ky) {
-                    const float* row = src + (size_t)reflect_idx(yy + ky - ks_y / 2, H) * W;
-                    float r = 0.f;
-                    for (int kx = 0; kx < ks_x; ++kx) r = fmaf(gx[kx], row[reflect_idx(xx + kx - ks_x / 2, W)], r);
-                    v = fmaf(gy[ky], r, v);
-                }
-                rowacc = fmaf(wx[b], v / (ny * nx), rowacc);
-            }
-            acc = fmaf(wy[a], rowacc, acc);
-        }
+        const float acc = clip_resample([=](int y) { return src + (size_t)y * W; }, oy, ox, H, W, out_hw, gy, gx, ks_y, ks_x, ny, nx);
         const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-        const float val = ((acc + 1.f) * 0.5f - mean) / sd;
+        const float val = clip_normalise(acc, mean, sd);
         const int py = oy / ps, ky = oy - py * ps, px = ox / ps, kx = ox - px * ps;
         out[((size_t)n * (1 + gp * gp) + 1 + py * gp + px) * ldo + (c * ps + ky) * ps + kx] = f32_to_bf16(val);
     }

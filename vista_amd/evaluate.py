@@ -15,7 +15,12 @@ to <save>/metrics_summary.json; both files describe this run only. The first --n
 every mean. A mean over frames of which one is identical to its ground truth (infinite PSNR) is infinite, and written as null.
 
 Not built: the IMG dataset (one picture repeated has no future to compare against) and several GPUs (WORLD_SIZE > 1) are refused by name; the
-natural multi-GPU form is scene i on rank i mod W with a merge of the records. Perceptual metrics that need a pretrained network are not built.
+natural multi-GPU form is scene i on rank i mod W with a merge of the records. LPIPS and FVD are not built: their weights are in no checkpoint.
+
+With the environment hook VISTA_EVAL_CLIP=1 the records also hold CLIP-space scores from the checkpoint's own image tower (vista_amd/perceptual.py;
+README "CLIP-space scores"): per scored frame `clip_sim`, `clip_step`, `clip_step_real`, their means over the predicted frames, the scene's
+`clip_mmd`, and in the summary the means over scenes, the horizon curves and the run-level `clip_mmd`. --compare then loads the tower alone from
+--config / --ckpt. Unset (or 0), nothing here changes.
 """
 import json
 import os
@@ -23,7 +28,7 @@ import re
 import sys
 import time
 
-from . import fidelity, frontdoor, sample
+from . import fidelity, frontdoor, perceptual, sample
 from .frontdoor import json_number, mean
 from ._lib import VistaHipError
 from . import sample_utils as SU
@@ -48,6 +53,7 @@ def check_run(opt, net_params=None):
     SU.sampler_name()   # (a bad VISTA_SAMPLER is refused by name, here)
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
     SU.png_format()     # (and a bad VISTA_PNG)
+    SU.eval_clip()      # (and a bad VISTA_EVAL_CLIP)
     if opt.height < fidelity.TAPS or opt.width < fidelity.TAPS:
         raise ValueError(f"--height {opt.height} --width {opt.width}: SSIM takes an {fidelity.TAPS} x {fidelity.TAPS} window")
     if opt.dataset == "IMG":
@@ -87,8 +93,9 @@ def frame_round(i, n_frames):
     return 0 if i < n_frames else 1 + (i - n_frames) // (n_frames - 3)
 
 
-def make_record(index, frame_list, report, *, seed, action, n_conds, n_rounds, n_frames, timings=None):
-    """The JSON record of one scene from its FidelityReport (one entry per scored frame)."""
+def make_record(index, frame_list, report, *, seed, action, n_conds, n_rounds, n_frames, timings=None, clip=None):
+    """The JSON record of one scene from its FidelityReport (one entry per scored frame). clip: the scene's perceptual.PerceptualReport, which
+    adds the clip_* keys (a NaN score is null, and so is a mean that holds one); None adds nothing."""
     scored = len(report.psnr)
     psnr, ssim = [float(v) for v in report.psnr], [float(v) for v in report.ssim]
     cond = [i for i in range(scored) if i < n_conds]
@@ -99,16 +106,34 @@ def make_record(index, frame_list, report, *, seed, action, n_conds, n_rounds, n
         if members:
             rounds.append({"round": r, "frames": len(members), "mean_psnr": json_number(mean([psnr[i] for i in members])),
                            "mean_ssim": json_number(mean([ssim[i] for i in members]))})
-    return {"index": int(index), "frames": [frame_list[0]], "seed": int(seed), "action": str(action), "n_conds": int(n_conds),
-            "n_rounds": int(n_rounds), "frames_scored": scored,
-            "psnr": [json_number(v) for v in psnr], "ssim": [json_number(v) for v in ssim], "sse": [[int(c) for c in row] for row in report.sse],
-            "cond": cond, "mean_psnr": json_number(mean([psnr[i] for i in pred])), "mean_ssim": json_number(mean([ssim[i] for i in pred])),
-            "rounds": rounds, "timings": frontdoor.rounded_timings(timings)}
+    record = {"index": int(index), "frames": [frame_list[0]], "seed": int(seed), "action": str(action), "n_conds": int(n_conds),
+              "n_rounds": int(n_rounds), "frames_scored": scored,
+              "psnr": [json_number(v) for v in psnr], "ssim": [json_number(v) for v in ssim], "sse": [[int(c) for c in row] for row in report.sse],
+              "cond": cond, "mean_psnr": json_number(mean([psnr[i] for i in pred])), "mean_ssim": json_number(mean([ssim[i] for i in pred])),
+              "rounds": rounds, "timings": frontdoor.rounded_timings(timings)}
+    if clip is None:
+        return record
+    if not len(clip.sim) == len(clip.step) == len(clip.step_real) == scored:
+        raise ValueError(f"make_record: the CLIP-space report holds {len(clip.sim)} frames, the fidelity report {scored}")
+    timings_at = record.pop("timings")   # (stays the last key)
+    scores = {"clip_sim": [float(v) for v in clip.sim], "clip_step": [float(v) for v in clip.step], "clip_step_real": [float(v) for v in clip.step_real]}
+    for key, values in scores.items():
+        record[key] = [json_number(v) for v in values]
+    for key, values in scores.items():   # (a first predicted frame steps from the last conditioning frame)
+        record["mean_" + key] = json_number(mean([values[i] for i in pred]))
+    record["clip_mmd"] = None if clip.mmd is None else perceptual.mmd_json(clip.mmd)
+    for r in rounds:
+        members = [i for i in pred if frame_round(i, n_frames) == r["round"]]
+        r["mean_clip_sim"] = json_number(mean([float(clip.sim[i]) for i in members]))
+    record["timings"] = timings_at
+    return record
 
 
-def summarize(records):
+def summarize(records, clip=None):
     """Means over scenes and the horizon curve: at each frame index the mean PSNR and SSIM over the scenes that scored that index as a predicted
-    (not a conditioning) frame. null where no scene did, or where a PSNR in the mean is infinite (written as null in the record)."""
+    (not a conditioning) frame. null where no scene did, or where a PSNR in the mean is infinite (written as null in the record).
+    clip: {"mmd": perceptual.mmd() over all predicted and real frames of the run (or None), "tower": perceptual.tower_info()} for records made
+    with clip=; adds the CLIP-space means, horizon curves and the run-level clip_mmd. None adds nothing."""
     def scene_mean(key):
         vals = [r[key] for r in records if r["frames_scored"] > len(r["cond"])]
         return None if not vals or any(v is None for v in vals) else json_number(mean(vals))
@@ -120,7 +145,19 @@ def summarize(records):
         for key in ("psnr", "ssim"):
             vals = [r[key][i] for r in has]
             horizon[key].append(None if not vals or any(v is None for v in vals) else json_number(mean(vals)))
-    return {"scenes": len(records), "mean_psnr": scene_mean("mean_psnr"), "mean_ssim": scene_mean("mean_ssim"), "horizon": horizon}
+    summary = {"scenes": len(records), "mean_psnr": scene_mean("mean_psnr"), "mean_ssim": scene_mean("mean_ssim"), "horizon": horizon}
+    if clip is None:
+        return summary
+    for key in ("mean_clip_sim", "mean_clip_step", "mean_clip_step_real"):
+        summary[key] = scene_mean(key)
+    for key in ("clip_sim", "clip_step"):
+        horizon[key] = []
+        for i in range(length):
+            vals = [r[key][i] for r in records if i < r["frames_scored"] and i not in r["cond"]]
+            horizon[key].append(None if not vals or any(v is None for v in vals) else json_number(mean(vals)))
+    summary["clip_mmd"] = None if clip["mmd"] is None else perceptual.mmd_json(clip["mmd"])
+    summary["clip"] = dict(clip["tower"])
+    return summary
 
 
 # ---- offline: the pictures of an earlier run ----------------------------------------------------------------------------------------------------
@@ -150,9 +187,16 @@ def compare(opt):
     check_world()
     if not 1 <= opt.n_conds:
         raise ValueError(f"--n_conds {opt.n_conds}: at least one conditioning frame")
+    ckpt = None
+    if SU.eval_clip():   # the tower alone, from --config / --ckpt: a checkpoint that is not there is refused before anything is read
+        ckpt = opt.ckpt or SU.VERSION2SPECS[opt.version]["ckpt"]
+        if not os.path.isfile(ckpt):
+            raise FileNotFoundError(f"--compare with VISTA_EVAL_CLIP=1: the checkpoint {ckpt} does not exist (--ckpt names the file whose "
+                                    "image tower scores the pictures)")
     scenes = picture_pairs(opt.compare)
     if not torch.cuda.is_available():
         raise VistaHipError("evaluate --compare: no GPU is visible; vista_amd runs on the MI355X only (no CPU / eager fallback)")
+    clip_run = perceptual.RunScores(perceptual.load_tower(opt.config, ckpt)) if ckpt is not None else None
     frontdoor.start_records(opt.compare, RECORDS_NAME)
     records = []
     for dataset, index, frames in scenes:
@@ -169,17 +213,33 @@ def compare(opt):
         t1 = time.perf_counter()
         report = fidelity.frame_metrics(stacks[0], stacks[1])
         timings = {"load": t1 - t0, "metrics": time.perf_counter() - t1}
+        clip = _clip_stage(clip_run, stacks[0], stacks[1], opt.n_conds, timings)
         record = make_record(index, [frames[0][2]], report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
-                             n_frames=opt.n_frames, timings=timings)
+                             n_frames=opt.n_frames, timings=timings, **clip)
         frontdoor.append_record(opt.compare, RECORDS_NAME, record)
         records.append(record)
         print(_scene_line(record), flush=True)
-    frontdoor.write_summary(opt.compare, SUMMARY_NAME, summarize(records))
+    frontdoor.write_summary(opt.compare, SUMMARY_NAME, _summary(records, clip_run))
     return 0
 
 
+def _clip_stage(clip_run, pred_u8, real_u8, n_conds, timings):
+    """The CLIP-space stage behind a scene's metrics -> the clip= keyword of make_record ({} without the hook: the call is the parent's)."""
+    if clip_run is None:
+        return {}
+    t0 = time.perf_counter()
+    report = clip_run.scene(pred_u8, real_u8, n_conds)   # (its copies to the host end the stage)
+    timings["clip"] = time.perf_counter() - t0
+    return {"clip": report}
+
+
+def _summary(records, clip_run):
+    return summarize(records) if clip_run is None else summarize(records, clip=clip_run.summary())
+
+
 def _scene_line(record):
-    shown = ", ".join(f"{k} " + ("null" if record[k] is None else f"{record[k]:.4f}") for k in ("mean_psnr", "mean_ssim"))
+    keys = ("mean_psnr", "mean_ssim") + (("mean_clip_sim",) if "mean_clip_sim" in record else ())
+    shown = ", ".join(f"{k} " + ("null" if record[k] is None else f"{record[k]:.4f}") for k in keys)
     return (f"evaluate {record['index']}: {record['frames_scored']} frames, {shown} | "
             + frontdoor.timings_text(record["timings"]))
 
@@ -198,7 +258,9 @@ def main(argv=None):
 def _evaluate_loop(opt):
     """The loop of vista_amd.sample with the metrics stage behind every scene."""
     import torch
+    from . import ops
     model = frontdoor.build_model(opt)
+    clip_run = perceptual.RunScores(perceptual.find_tower(model)) if SU.eval_clip() else None
     frontdoor.start_records(opt.save, RECORDS_NAME)
     records = []
     for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt, n_scenes=opt.n_scenes):
@@ -217,18 +279,22 @@ def _evaluate_loop(opt):
         torch.cuda.synchronize()
         timings["load"] = timings.get("load", 0.0) + time.perf_counter() - t0
         t0 = time.perf_counter()
-        report = fidelity.frame_metrics(samples[:scored].float(), real[:scored].float())   # (its copy to the host ends the stage)
+        pred_m, real_m = samples[:scored].float(), real[:scored].float()
+        if clip_run is not None:   # both stacks to 8 bit once: the same bytes go to the fidelity and to the CLIP-space stage
+            pred_m, real_m = ops.frames_to_u8(pred_m, real=False), ops.frames_to_u8(real_m, real=True)
+        report = fidelity.frame_metrics(pred_m, real_m)   # (its copy to the host ends the stage)
         timings["metrics"] = time.perf_counter() - t0
+        clip = _clip_stage(clip_run, pred_m, real_m, opt.n_conds, timings)
         if not opt.no_pictures:
             t0 = time.perf_counter()
             frontdoor.save_pictures(opt.save, opt.dataset, sample_index, virtual=samples, real=real)
             timings["save"] = time.perf_counter() - t0
         record = make_record(sample_index, frame_list, report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
-                             n_frames=opt.n_frames, timings=timings)
+                             n_frames=opt.n_frames, timings=timings, **clip)
         frontdoor.append_record(opt.save, RECORDS_NAME, record)
         records.append(record)
         print(_scene_line(record), flush=True)
-    frontdoor.write_summary(opt.save, SUMMARY_NAME, summarize(records))
+    frontdoor.write_summary(opt.save, SUMMARY_NAME, _summary(records, clip_run))
     return 0
 
 

@@ -3,7 +3,7 @@
 `frame_metrics(pred, real)` converts float frames to 8 bit the way `perform_save_locally` does (ops.frames_to_u8), runs vk_frame_fidelity_u8
 (csrc/fidelity.hip) over the two stacks and forms PSNR and the mean SSIM on the host in float64. SSIM is Wang, Bovik, Sheikh and Simoncelli
 (2004): an 11-tap Gaussian window (sigma 1.5), valid positions only, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, per channel, then averaged over
-the three channels. Perceptual metrics that need a pretrained network (LPIPS, FVD) are not built here.
+the three channels. CLIP-space scores from the checkpoint's own image tower are in perceptual.py; LPIPS and FVD are not built.
 """
 import ctypes as C
 from dataclasses import dataclass

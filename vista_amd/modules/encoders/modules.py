@@ -251,13 +251,16 @@ class FrozenOpenCLIPImageEmbedder(AbstractEmbModel, Packable):
         return ops.clip_preprocess_patches(x.float(), out_hw=g["image"], patch=g["patch"], antialias=self.antialias)
 
     def _visual(self, img):
+        return self._visual_patches(self.preprocess(img), img.shape[0])
+
+    def _visual_patches(self, patches, n):
+        """The tower from the patch-embedding GEMM's A operand of n images (what preprocess returns) to their (n, embed) fp32 embeddings."""
         g, v = self.geometry, self.model.visual
         pk = self.packed()
-        n = img.shape[0]
         n_tok, width, heads = (g["image"] // g["patch"]) ** 2 + 1, g["width"], g["heads"]
         if n not in pk["pos_rep"]:
             pk["pos_rep"] = {n: pk["pos"].repeat(n, 1)}  # (n*n_tok, width) bf16, kept for the batch size in use
-        t = ops.linear(self.preprocess(img), pk["conv1"], res1=pk["pos_rep"][n])
+        t = ops.linear(patches, pk["conv1"], res1=pk["pos_rep"][n])
         x = ops.layernorm(t, v.ln_pre.weight, v.ln_pre.bias, v.ln_pre.eps)   # the residual stream starts normalised (ln_pre)
         st = ops.rowstats(x)
         for blk in pk["blocks"]:
@@ -282,6 +285,16 @@ class FrozenOpenCLIPImageEmbedder(AbstractEmbModel, Packable):
         if n > 1 and bool((img[1:] == img[:1]).flatten(1).all()):
             return self._visual(img[:1]).expand(n, -1).contiguous()
         return self._visual(img)
+
+    @torch.no_grad()
+    @ops.bf16_storage
+    def embed_patches(self, patches, n):
+        """(n, embed) fp32 embeddings of n images from their prepared patch operand (ops.clip_preprocess_patches or its uint8 form): the tower
+        of `forward` behind its preprocessing, for callers that hold the frames as bytes (vista_amd/perceptual.py)."""
+        rows = n * ((self.geometry["image"] // self.geometry["patch"]) ** 2 + 1)
+        if patches.dim() != 2 or patches.shape[0] != rows:
+            raise ValueError(f"embed_patches: the patch operand of {n} images has {rows} rows, got {tuple(patches.shape)}")
+        return self._visual_patches(patches, n)
 
     @torch.no_grad()
     def forward(self, image, no_dropout=False):

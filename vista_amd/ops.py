@@ -1630,6 +1630,73 @@ def frame_fidelity_u8(a, b):
     return sse, ssim_sum
 
 
+# ---- CLIP-space scores (csrc/perceptual.hip) ----
+EMBED_MAX_ROWS, EMBED_MAX_DIM, EMBED_MMD_TILE = 1 << 20, 1 << 16, 64   # VK_EMBED_* of include/vista_hip.h
+
+
+def clip_preprocess_patches_u8(frames_u8, out_hw=224, patch=14, kpad=None, antialias=True, mean=CLIP_MEAN, std=CLIP_STD):
+    """frames_u8 (n, H, W, 3) uint8, dense, on the GPU (the bytes frames_to_u8 writes) -> what clip_preprocess_patches returns for
+    `frames_u8.permute(0, 3, 1, 2).float() / 127.5 - 1.0` (an IEEE fp32 division), bit for bit, without the fp32 frames: the bytes are
+    converted once, in LDS (vk_clip_preprocess_patches_u8). Any width and any base address are taken. Nothing is synchronised."""
+    _need(frames_u8, torch.uint8, "frames_u8")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.shape[0] < 1:
+        _refuse("frames_u8", frames_u8, "must be (n, H, W, 3), n >= 1")
+    if not frames_u8.is_contiguous():
+        _refuse("frames_u8", frames_u8, "must be a dense (contiguous) stack")
+    n, H, W, _ = frames_u8.shape
+    g = out_hw // patch
+    kp = kpad or ceil_to(3 * patch * patch, 64)
+    out = torch.zeros((n * (1 + g * g), kp), dtype=BF16, device=frames_u8.device)
+    down = antialias and max(H / out_hw, W / out_hw) > 1  # kornia blurs BOTH axes as soon as either one is downscaled
+    (sy, ky), (sx, kx) = (antialias_blur_params(H, out_hw), antialias_blur_params(W, out_hw)) if down else ((1.0, 1), (1.0, 1))
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    check(_lib.load().vk_clip_preprocess_patches_u8(_p(frames_u8), _p(out), n, H, W, out_hw, patch, kp, sy, sx, ky, kx, m3, s3, _stream()),
+          "vk_clip_preprocess_patches_u8")
+    return out
+
+
+def _embedding(t, name, cols=None):
+    _need(t, F32, name)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or (cols is not None and t.shape[1] != cols):
+        _refuse(name, t, "must be (rows, d) with rows, d >= 1" + ("" if cols is None else f" and d = {cols}"))
+    if not t.is_contiguous():
+        _refuse(name, t, "must be dense (contiguous)")
+    if t.shape[0] > EMBED_MAX_ROWS or t.shape[1] > EMBED_MAX_DIM:
+        _refuse(name, t, f"at most {EMBED_MAX_ROWS} rows of at most {EMBED_MAX_DIM} columns")
+
+
+def embed_row_stats(a, b):
+    """a, b (n, d) fp32, dense, on the GPU -> (n, 3) float64 on the GPU: per row a.b, a.a, b.b, products of fp32 values summed in fp64 in one
+    fixed order (vk_embed_row_stats). `a is b` gives three equal bit patterns per row. Nothing is synchronised."""
+    _embedding(a, "a")
+    _embedding(b, "b", cols=a.shape[1])
+    if a.shape != b.shape or a.device != b.device:
+        _refuse("b", b, f"must pair up with a {tuple(a.shape)} on {a.device}")
+    out = torch.empty((a.shape[0], 3), dtype=torch.float64, device=a.device)
+    check(_lib.load().vk_embed_row_stats(_p(a), _p(b), _p(out), a.shape[0], a.shape[1], _stream()), "vk_embed_row_stats")
+    return out
+
+
+def embed_mmd_sums(x, y, sigma):
+    """x (m, d), y (n, d) fp32, dense, on the GPU -> 3 float64 on the GPU: the sums of 1 - k over the pairs i < j of x^, over the pairs of y^,
+    and over every (x^_i, y^_j); u^ = u / |u|, k(u, v) = exp(-|u - v|^2 / (2 sigma^2)) (vk_embed_mmd_sums: fp32 differences, expm1, fp64
+    sums in a fixed order). Nothing is synchronised."""
+    _embedding(x, "x")
+    _embedding(y, "y", cols=x.shape[1])
+    if x.device != y.device:
+        _refuse("y", y, f"must be on {x.device}")
+    if not (isinstance(sigma, (int, float)) and 0 < sigma < math.inf):
+        raise ValueError(f"embed_mmd_sums: sigma must be a positive finite number, got {sigma!r}")
+    (m, d), n = x.shape, y.shape[0]
+    lib = _lib.load()
+    ws_bytes = lib.vk_embed_mmd_ws_bytes(m, n, d)
+    check(min(ws_bytes, 0), "vk_embed_mmd_ws_bytes")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=x.device)
+    out = torch.empty(3, dtype=torch.float64, device=x.device)
+    check(lib.vk_embed_mmd_sums(_p(x), _p(y), _p(out), _p(ws), m, n, d, float(sigma), _stream()), "vk_embed_mmd_sums")
+    return out
+
+
 # ---- exchange packing of the frame-sharded step (csrc/reshard.hip, ABI v9) ----
 def row_boxes(boxes):
     """A list of (src_row, dst_row, src_stride_b, src_stride_t, dst_stride_b, dst_stride_t, nb, nt, ns) tuples -> the VkRowBoxes the library
