@@ -574,6 +574,44 @@ int vk_embed_row_stats(const float* a, const float* b, double* out, int32_t n, i
 int vk_embed_mmd_ws_bytes(int32_t m, int32_t n, int32_t d);
 int vk_embed_mmd_sums(const float* x, const float* y, double* out3, void* ws, int32_t m, int32_t n, int32_t d, float sigma, void* stream);
 
+/* ------------------------------------------------------------------ motion scores (csrc/flow.hip)
+ * Added under ABI v9 without a version step: purely additive, so vk_abi_version() stays 9. Integers only, from the bytes to the sums: two calls
+ * on the same input return the same bits, and so does a plain restatement on the host. Storage-type independent: the same code is linked into
+ * both libraries. The entry points allocate nothing and synchronise nothing.
+ *
+ * The flow is hierarchical block matching on 8-bit luma, defined exactly:
+ *   luma      Y = (77 R + 150 G + 29 B + 128) >> 8.
+ *   pyramid   VK_FLOW_LEVELS levels; level l + 1 is the 2 x 2 mean of level l, (a + b + c + d + 2) >> 2.
+ *   blocks    VK_FLOW_BLOCK x VK_FLOW_BLOCK pixels at every level; block (by, bx) of level l has the parent (by >> 1, bx >> 1) at level l + 1.
+ *   cost      of a vector (vy, vx) for a block of frame i at one level: the sum of absolute differences (SAD) of the block's 64 luma values
+ *             against frame i + 1's values at (y + vy, x + vx), both coordinates clamped to the image.
+ *   search    level 2: every (dy, dx) in [-7, 7]^2 around zero. Levels 1 and 0: twice the parent's vector plus an increment in [-2, 2]^2.
+ *   choice    the smallest (SAD, |dy| + |dx| of the increment, dy, dx), compared lexicographically.
+ * A translation of up to 30 px per frame step is within reach (4 * 7 + 2); beyond it the coarse search saturates.
+ *
+ * vk_flow_luma_pyramid_u8: frames (n, H, W, 3) uint8, dense -> pyr: level 0 of all frames (n, H, W), then level 1 (n, H/2, W/2), then level 2
+ * (n, H/4, W/4), vk_flow_pyramid_bytes(n, H, W) = n * H * W * 21 / 16 bytes in all, the caller's.
+ * vk_block_flow_u8: pyr of n >= 2 frames -> for every pair (i, i + 1), i < n - 1, and level-0 block:
+ *   flow (n - 1, H/8, W/8, 2) int16: (vy, vx) in pixels: content at (y, x) of frame i is found at (y + vy, x + vx) of frame i + 1; |v| <= 34
+ *   sad  (n - 1, H/8, W/8, 2) uint16: the block's SAD at that vector, and its SAD at zero displacement (both at most 16320)
+ * vk_flow_pair_sums: flow, sad (pairs, blocks, 2) as above, flow_ref likewise or NULL -> out (pairs, 5) int64: per pair the number of blocks
+ * with a non-zero vector, sum(vy^2 + vx^2), sum SAD, sum SAD at zero, and sum((vy - vy_ref)^2 + (vx - vx_ref)^2) (0 where flow_ref is NULL).
+ *   VK_EINVAL, before any launch: a NULL pointer (but flow_ref); frames / pyr / flow / sad / flow_ref not 4-byte or out not 8-byte aligned; H or
+ *   W not a positive multiple of 32 or above VK_FLOW_MAX_SIDE (checked before any product is formed: no extent can wrap); n < 1
+ *   (vk_block_flow_u8: n < 2), n > VK_FLOW_MAX_FRAMES; a pyramid of more than 2^31 - 1 bytes; pairs or
+ *   blocks < 1, pairs * blocks > 2^31 - 1. */
+#define VK_FLOW_BLOCK 8
+#define VK_FLOW_LEVELS 3
+#define VK_FLOW_COARSE_RANGE 7
+#define VK_FLOW_REFINE_RANGE 2
+#define VK_FLOW_MAX_FRAMES 65535
+#define VK_FLOW_MAX_SIDE 65536
+int vk_flow_pyramid_bytes(int32_t n, int32_t H, int32_t W);
+int vk_flow_luma_pyramid_u8(const void* frames, void* pyr, int32_t n, int32_t H, int32_t W, void* stream);
+int vk_block_flow_u8(const void* pyr, int16_t* flow, uint16_t* sad, int32_t n, int32_t H, int32_t W, void* stream);
+int vk_flow_pair_sums(const int16_t* flow, const uint16_t* sad, const int16_t* flow_ref /* or NULL */, int64_t* out, int32_t pairs,
+                      int32_t blocks, void* stream);
+
 /* ------------------------------------------------------------------ exchange packing of the frame-sharded step (ABI v9; csrc/reshard.hip)
  * Storage-type independent: the same code is linked into both libraries.
  *

@@ -158,6 +158,10 @@ SIGNATURES = {
     "vk_embed_row_stats": [_vp, _vp, _vp, _i32, _i32, _vp],
     "vk_embed_mmd_ws_bytes": [_i32, _i32, _i32],
     "vk_embed_mmd_sums": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp],
+    "vk_flow_pyramid_bytes": [_i32, _i32, _i32],
+    "vk_flow_luma_pyramid_u8": [_vp, _vp, _i32, _i32, _i32, _vp],
+    "vk_block_flow_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    "vk_flow_pair_sums": [_vp, _vp, _vp, _vp, _i32, _i32, _vp],
     "vk_copy_row_boxes": [_vp, _vp, C.POINTER(VkRowBoxes), _i64, _i64, _i32, _vp],
     "vk_stroke_overlay_u8": [_vp, _vp, _vp, C.POINTER(VkStrokePlan), _i32, _i32, _i32, _vp],
     "vk_loss_noise_input": [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp],

@@ -21,6 +21,12 @@ With the environment hook VISTA_EVAL_CLIP=1 the records also hold CLIP-space sco
 README "CLIP-space scores"): per scored frame `clip_sim`, `clip_step`, `clip_step_real`, their means over the predicted frames, the scene's
 `clip_mmd`, and in the summary the means over scenes, the horizon curves and the run-level `clip_mmd`. --compare then loads the tower alone from
 --config / --ckpt. Unset (or 0), nothing here changes.
+
+With the environment hook VISTA_EVAL_MOTION=1 the records also hold motion scores from block-matching optical flow on the same bytes
+(vista_amd/motion.py; README "Motion scores"): per scored frame `flow_rms`, `flow_rms_real`, `flow_epe`, `flow_moving`, `warp_err`,
+`warp_err_real` (the step from the frame before; entry 0 is null), their means over the predicted frames, a `mean_flow_epe` per round, and in
+the summary the means over scenes and the horizon curves of the first three. --compare needs nothing more for it: no model, no checkpoint; pictures
+whose sides are not multiples of 32 are refused by name. Unset (or 0), nothing here changes.
 """
 import json
 import os
@@ -28,7 +34,7 @@ import re
 import sys
 import time
 
-from . import fidelity, frontdoor, perceptual, sample
+from . import fidelity, frontdoor, motion, perceptual, sample
 from .frontdoor import json_number, mean
 from ._lib import VistaHipError
 from . import sample_utils as SU
@@ -54,6 +60,8 @@ def check_run(opt, net_params=None):
     SU.video_format()   # (and a bad VISTA_VIDEO or VISTA_VIDEO_QUALITY)
     SU.png_format()     # (and a bad VISTA_PNG)
     SU.eval_clip()      # (and a bad VISTA_EVAL_CLIP)
+    if SU.eval_motion():   # (and a bad VISTA_EVAL_MOTION; check_sizes left multiples of 64 only)
+        motion.check_size(opt.height, opt.width, f"--height {opt.height} --width {opt.width} with VISTA_EVAL_MOTION=1")
     if opt.height < fidelity.TAPS or opt.width < fidelity.TAPS:
         raise ValueError(f"--height {opt.height} --width {opt.width}: SSIM takes an {fidelity.TAPS} x {fidelity.TAPS} window")
     if opt.dataset == "IMG":
@@ -93,9 +101,15 @@ def frame_round(i, n_frames):
     return 0 if i < n_frames else 1 + (i - n_frames) // (n_frames - 3)
 
 
-def make_record(index, frame_list, report, *, seed, action, n_conds, n_rounds, n_frames, timings=None, clip=None):
+# record key -> MotionReport attribute, in the order the keys are written
+MOTION_KEYS = {"flow_rms": "rms", "flow_rms_real": "rms_real", "flow_epe": "epe", "flow_moving": "moving", "warp_err": "warp_err",
+               "warp_err_real": "warp_err_real"}
+
+
+def make_record(index, frame_list, report, *, seed, action, n_conds, n_rounds, n_frames, timings=None, clip=None, motion=None):
     """The JSON record of one scene from its FidelityReport (one entry per scored frame). clip: the scene's perceptual.PerceptualReport, which
-    adds the clip_* keys (a NaN score is null, and so is a mean that holds one); None adds nothing."""
+    adds the clip_* keys (a NaN score is null, and so is a mean that holds one); None adds nothing. motion: the scene's motion.MotionReport of
+    both stacks, which adds the MOTION_KEYS after them (entry 0, which has no predecessor, is null); None adds nothing."""
     scored = len(report.psnr)
     psnr, ssim = [float(v) for v in report.psnr], [float(v) for v in report.ssim]
     cond = [i for i in range(scored) if i < n_conds]
@@ -111,29 +125,45 @@ def make_record(index, frame_list, report, *, seed, action, n_conds, n_rounds, n
               "psnr": [json_number(v) for v in psnr], "ssim": [json_number(v) for v in ssim], "sse": [[int(c) for c in row] for row in report.sse],
               "cond": cond, "mean_psnr": json_number(mean([psnr[i] for i in pred])), "mean_ssim": json_number(mean([ssim[i] for i in pred])),
               "rounds": rounds, "timings": frontdoor.rounded_timings(timings)}
-    if clip is None:
+    if clip is None and motion is None:
         return record
-    if not len(clip.sim) == len(clip.step) == len(clip.step_real) == scored:
-        raise ValueError(f"make_record: the CLIP-space report holds {len(clip.sim)} frames, the fidelity report {scored}")
     timings_at = record.pop("timings")   # (stays the last key)
-    scores = {"clip_sim": [float(v) for v in clip.sim], "clip_step": [float(v) for v in clip.step], "clip_step_real": [float(v) for v in clip.step_real]}
-    for key, values in scores.items():
-        record[key] = [json_number(v) for v in values]
-    for key, values in scores.items():   # (a first predicted frame steps from the last conditioning frame)
-        record["mean_" + key] = json_number(mean([values[i] for i in pred]))
-    record["clip_mmd"] = None if clip.mmd is None else perceptual.mmd_json(clip.mmd)
-    for r in rounds:
-        members = [i for i in pred if frame_round(i, n_frames) == r["round"]]
-        r["mean_clip_sim"] = json_number(mean([float(clip.sim[i]) for i in members]))
+    if clip is not None:
+        if not len(clip.sim) == len(clip.step) == len(clip.step_real) == scored:
+            raise ValueError(f"make_record: the CLIP-space report holds {len(clip.sim)} frames, the fidelity report {scored}")
+        scores = {"clip_sim": [float(v) for v in clip.sim], "clip_step": [float(v) for v in clip.step], "clip_step_real": [float(v) for v in clip.step_real]}
+        for key, values in scores.items():
+            record[key] = [json_number(v) for v in values]
+        for key, values in scores.items():   # (a first predicted frame steps from the last conditioning frame)
+            record["mean_" + key] = json_number(mean([values[i] for i in pred]))
+        record["clip_mmd"] = None if clip.mmd is None else perceptual.mmd_json(clip.mmd)
+        for r in rounds:
+            members = [i for i in pred if frame_round(i, n_frames) == r["round"]]
+            r["mean_clip_sim"] = json_number(mean([float(clip.sim[i]) for i in members]))
+    if motion is not None:
+        columns = {key: getattr(motion, attr) for key, attr in MOTION_KEYS.items()}
+        if any(v is None for v in columns.values()) or not all(len(v) == scored for v in columns.values()):
+            held = "no real stack" if motion.epe is None else f"{len(motion.rms)} frames"
+            raise ValueError(f"make_record: the motion report holds {held}, the fidelity report {scored} frames of both stacks")
+        scores = {key: [float(v) for v in values] for key, values in columns.items()}
+        for key, values in scores.items():   # (entry 0 has no predecessor: null)
+            record[key] = [json_number(v) for v in values]
+        for key, values in scores.items():   # (a first predicted frame steps from the last conditioning frame)
+            record["mean_" + key] = json_number(mean([values[i] for i in pred]))
+        for r in rounds:
+            members = [i for i in pred if frame_round(i, n_frames) == r["round"]]
+            r["mean_flow_epe"] = json_number(mean([scores["flow_epe"][i] for i in members]))
     record["timings"] = timings_at
     return record
 
 
-def summarize(records, clip=None):
+def summarize(records, clip=None, motion=None):
     """Means over scenes and the horizon curve: at each frame index the mean PSNR and SSIM over the scenes that scored that index as a predicted
     (not a conditioning) frame. null where no scene did, or where a PSNR in the mean is infinite (written as null in the record).
     clip: {"mmd": perceptual.mmd() over all predicted and real frames of the run (or None), "tower": perceptual.tower_info()} for records made
-    with clip=; adds the CLIP-space means, horizon curves and the run-level clip_mmd. None adds nothing."""
+    with clip=; adds the CLIP-space means, horizon curves and the run-level clip_mmd. None adds nothing.
+    motion: motion.motion_info() for records made with motion=; adds the means over scenes of the motion scores, the horizon curves of flow_rms,
+    flow_rms_real and flow_epe, and the dict itself under "motion". None adds nothing."""
     def scene_mean(key):
         vals = [r[key] for r in records if r["frames_scored"] > len(r["cond"])]
         return None if not vals or any(v is None for v in vals) else json_number(mean(vals))
@@ -146,17 +176,25 @@ def summarize(records, clip=None):
             vals = [r[key][i] for r in has]
             horizon[key].append(None if not vals or any(v is None for v in vals) else json_number(mean(vals)))
     summary = {"scenes": len(records), "mean_psnr": scene_mean("mean_psnr"), "mean_ssim": scene_mean("mean_ssim"), "horizon": horizon}
-    if clip is None:
-        return summary
-    for key in ("mean_clip_sim", "mean_clip_step", "mean_clip_step_real"):
-        summary[key] = scene_mean(key)
-    for key in ("clip_sim", "clip_step"):
+
+    def curve(key):
         horizon[key] = []
         for i in range(length):
             vals = [r[key][i] for r in records if i < r["frames_scored"] and i not in r["cond"]]
             horizon[key].append(None if not vals or any(v is None for v in vals) else json_number(mean(vals)))
-    summary["clip_mmd"] = None if clip["mmd"] is None else perceptual.mmd_json(clip["mmd"])
-    summary["clip"] = dict(clip["tower"])
+    if clip is not None:
+        for key in ("mean_clip_sim", "mean_clip_step", "mean_clip_step_real"):
+            summary[key] = scene_mean(key)
+        for key in ("clip_sim", "clip_step"):
+            curve(key)
+        summary["clip_mmd"] = None if clip["mmd"] is None else perceptual.mmd_json(clip["mmd"])
+        summary["clip"] = dict(clip["tower"])
+    if motion is not None:
+        for key in MOTION_KEYS:
+            summary["mean_" + key] = scene_mean("mean_" + key)
+        for key in ("flow_rms", "flow_rms_real", "flow_epe"):
+            curve(key)
+        summary["motion"] = dict(motion)
     return summary
 
 
@@ -193,7 +231,14 @@ def compare(opt):
         if not os.path.isfile(ckpt):
             raise FileNotFoundError(f"--compare with VISTA_EVAL_CLIP=1: the checkpoint {ckpt} does not exist (--ckpt names the file whose "
                                     "image tower scores the pictures)")
+    motion_run = motion.RunScores() if SU.eval_motion() else None   # (a bad VISTA_EVAL_MOTION is refused by name, before anything is read)
     scenes = picture_pairs(opt.compare)
+    if motion_run is not None:   # every picture's size from its header, before anything is scored
+        for dataset, index, frames in scenes:
+            for entry in frames:
+                for path in entry[1:]:
+                    with Image.open(path) as im:
+                        motion.check_size(im.height, im.width, f"--compare {opt.compare} with VISTA_EVAL_MOTION=1: {os.path.basename(path)}")
     if not torch.cuda.is_available():
         raise VistaHipError("evaluate --compare: no GPU is visible; vista_amd runs on the MI355X only (no CPU / eager fallback)")
     clip_run = perceptual.RunScores(perceptual.load_tower(opt.config, ckpt)) if ckpt is not None else None
@@ -213,13 +258,13 @@ def compare(opt):
         t1 = time.perf_counter()
         report = fidelity.frame_metrics(stacks[0], stacks[1])
         timings = {"load": t1 - t0, "metrics": time.perf_counter() - t1}
-        clip = _clip_stage(clip_run, stacks[0], stacks[1], opt.n_conds, timings)
+        more = {**_clip_stage(clip_run, stacks[0], stacks[1], opt.n_conds, timings), **_motion_stage(motion_run, stacks[0], stacks[1], timings)}
         record = make_record(index, [frames[0][2]], report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
-                             n_frames=opt.n_frames, timings=timings, **clip)
+                             n_frames=opt.n_frames, timings=timings, **more)
         frontdoor.append_record(opt.compare, RECORDS_NAME, record)
         records.append(record)
         print(_scene_line(record), flush=True)
-    frontdoor.write_summary(opt.compare, SUMMARY_NAME, _summary(records, clip_run))
+    frontdoor.write_summary(opt.compare, SUMMARY_NAME, _summary(records, clip_run, motion_run))
     return 0
 
 
@@ -233,12 +278,26 @@ def _clip_stage(clip_run, pred_u8, real_u8, n_conds, timings):
     return {"clip": report}
 
 
-def _summary(records, clip_run):
-    return summarize(records) if clip_run is None else summarize(records, clip=clip_run.summary())
+def _motion_stage(motion_run, pred_u8, real_u8, timings):
+    """The motion stage behind a scene's metrics -> the motion= keyword of make_record ({} without the hook: the call is the parent's)."""
+    if motion_run is None:
+        return {}
+    t0 = time.perf_counter()
+    report = motion_run.scene(pred_u8, real_u8)   # (its copies to the host end the stage)
+    timings["motion"] = time.perf_counter() - t0
+    return {"motion": report}
+
+
+def _summary(records, clip_run, motion_run=None):
+    more = {} if clip_run is None else {"clip": clip_run.summary()}
+    if motion_run is not None:
+        more["motion"] = motion_run.summary()
+    return summarize(records, **more)
 
 
 def _scene_line(record):
     keys = ("mean_psnr", "mean_ssim") + (("mean_clip_sim",) if "mean_clip_sim" in record else ())
+    keys += ("mean_flow_epe",) if "mean_flow_epe" in record else ()
     shown = ", ".join(f"{k} " + ("null" if record[k] is None else f"{record[k]:.4f}") for k in keys)
     return (f"evaluate {record['index']}: {record['frames_scored']} frames, {shown} | "
             + frontdoor.timings_text(record["timings"]))
@@ -261,6 +320,7 @@ def _evaluate_loop(opt):
     from . import ops
     model = frontdoor.build_model(opt)
     clip_run = perceptual.RunScores(perceptual.find_tower(model)) if SU.eval_clip() else None
+    motion_run = motion.RunScores() if SU.eval_motion() else None
     frontdoor.start_records(opt.save, RECORDS_NAME)
     records = []
     for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt, n_scenes=opt.n_scenes):
@@ -280,21 +340,21 @@ def _evaluate_loop(opt):
         timings["load"] = timings.get("load", 0.0) + time.perf_counter() - t0
         t0 = time.perf_counter()
         pred_m, real_m = samples[:scored].float(), real[:scored].float()
-        if clip_run is not None:   # both stacks to 8 bit once: the same bytes go to the fidelity and to the CLIP-space stage
+        if clip_run is not None or motion_run is not None:   # both stacks to 8 bit once: the same bytes go to every metrics stage
             pred_m, real_m = ops.frames_to_u8(pred_m, real=False), ops.frames_to_u8(real_m, real=True)
         report = fidelity.frame_metrics(pred_m, real_m)   # (its copy to the host ends the stage)
         timings["metrics"] = time.perf_counter() - t0
-        clip = _clip_stage(clip_run, pred_m, real_m, opt.n_conds, timings)
+        more = {**_clip_stage(clip_run, pred_m, real_m, opt.n_conds, timings), **_motion_stage(motion_run, pred_m, real_m, timings)}
         if not opt.no_pictures:
             t0 = time.perf_counter()
             frontdoor.save_pictures(opt.save, opt.dataset, sample_index, virtual=samples, real=real)
             timings["save"] = time.perf_counter() - t0
         record = make_record(sample_index, frame_list, report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
-                             n_frames=opt.n_frames, timings=timings, **clip)
+                             n_frames=opt.n_frames, timings=timings, **more)
         frontdoor.append_record(opt.save, RECORDS_NAME, record)
         records.append(record)
         print(_scene_line(record), flush=True)
-    frontdoor.write_summary(opt.save, SUMMARY_NAME, _summary(records, clip_run))
+    frontdoor.write_summary(opt.save, SUMMARY_NAME, _summary(records, clip_run, motion_run))
     return 0
 
 

@@ -1630,6 +1630,89 @@ def frame_fidelity_u8(a, b):
     return sse, ssim_sum
 
 
+# ---- motion scores (csrc/flow.hip) ----
+FLOW_BLOCK, FLOW_LEVELS, FLOW_COARSE_RANGE, FLOW_REFINE_RANGE = 8, 3, 7, 2   # VK_FLOW_* of include/vista_hip.h
+FLOW_MAX_FRAMES, FLOW_MAX_SIDE = 65535, 65536
+FLOW_TILE = FLOW_BLOCK << (FLOW_LEVELS - 1)   # 32: the level-0 side of a level-2 block; H and W are multiples of it
+
+
+def flow_check_shape(what, n, H, W):
+    """The one refusal, by name, of a stack the flow kernels do not take (vista_amd/motion.py and evaluate ask it too, before any launch)."""
+    if H < FLOW_TILE or W < FLOW_TILE or H % FLOW_TILE or W % FLOW_TILE:
+        raise ValueError(f"{what}: {H} x {W} frames: the block-matching flow takes heights and widths that are multiples of {FLOW_TILE} "
+                         f"({FLOW_BLOCK}-px blocks on {FLOW_LEVELS} pyramid levels)")
+    if n > FLOW_MAX_FRAMES or H > FLOW_MAX_SIDE or W > FLOW_MAX_SIDE or n * H * W * 21 // 16 > 0x7fffffff:
+        raise ValueError(f"{what}: {n} frames of {H} x {W}: at most {FLOW_MAX_FRAMES} frames, sides of {FLOW_MAX_SIDE} and a pyramid of "
+                         "2^31 - 1 bytes a call")
+
+
+def flow_luma_pyramid_u8(frames_u8):
+    """frames_u8 (n, H, W, 3) uint8, dense, on the GPU, n >= 1, H and W multiples of 32 -> the three luma levels of every frame in one flat
+    uint8 tensor: level 0 (n, H, W), then level 1 (n, H/2, W/2), then level 2 (n, H/4, W/4) (vk_flow_luma_pyramid_u8; flow_pyramid_levels
+    gives the views). Nothing is synchronised."""
+    _need(frames_u8, torch.uint8, "frames_u8")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.shape[0] < 1:
+        raise ValueError(f"flow_luma_pyramid_u8: expected an (n, H, W, 3) uint8 stack of at least one frame, got {tuple(frames_u8.shape)}")
+    if not frames_u8.is_contiguous():
+        raise ValueError("flow_luma_pyramid_u8: frames_u8 must be a dense (contiguous) stack")
+    n, H, W, _ = frames_u8.shape
+    flow_check_shape("flow_luma_pyramid_u8", n, H, W)
+    frames_u8 = frames_u8 if frames_u8.data_ptr() % 4 == 0 else frames_u8.clone()   # (a dense view into another tensor's storage may start anywhere)
+    pyr = torch.empty(n * H * W * 21 // 16, dtype=torch.uint8, device=frames_u8.device)
+    check(_lib.load().vk_flow_luma_pyramid_u8(_p(frames_u8), _p(pyr), n, H, W, _stream()), "vk_flow_luma_pyramid_u8")
+    return pyr
+
+
+def flow_pyramid_levels(pyr, n, H, W):
+    """The three levels of flow_luma_pyramid_u8's tensor as (n, H, W), (n, H/2, W/2) and (n, H/4, W/4) views."""
+    a, b = n * H * W, n * H * W // 4
+    return pyr[:a].view(n, H, W), pyr[a:a + b].view(n, H // 2, W // 2), pyr[a + b:].view(n, H // 4, W // 4)
+
+
+def block_flow_u8(pyr, n, H, W):
+    """pyr: flow_luma_pyramid_u8 of n >= 2 frames of (H, W) -> (flow (n - 1, H/8, W/8, 2) int16, sad (n - 1, H/8, W/8, 2) uint16): per pair of
+    consecutive frames and 8 x 8 block the vector (vy, vx) in pixels -- content at (y, x) of frame i is found at (y + vy, x + vx) of frame
+    i + 1 --, its SAD and the block's SAD at zero displacement (vk_block_flow_u8). Nothing is synchronised."""
+    _need(pyr, torch.uint8, "pyr")
+    n, H, W = int(n), int(H), int(W)
+    if n < 2:
+        raise ValueError(f"block_flow_u8: {n} frames hold no pair of consecutive frames")
+    flow_check_shape("block_flow_u8", n, H, W)
+    if pyr.dim() != 1 or pyr.numel() != n * H * W * 21 // 16 or not pyr.is_contiguous():
+        raise ValueError(f"block_flow_u8: pyr must be the flat, dense tensor flow_luma_pyramid_u8 returns for {n} frames of {H} x {W} "
+                         f"({n * H * W * 21 // 16} bytes), got {tuple(pyr.shape)}")
+    pyr = pyr if pyr.data_ptr() % 4 == 0 else pyr.clone()
+    flow = torch.empty((n - 1, H // FLOW_BLOCK, W // FLOW_BLOCK, 2), dtype=torch.int16, device=pyr.device)
+    sad = torch.empty((n - 1, H // FLOW_BLOCK, W // FLOW_BLOCK, 2), dtype=torch.uint16, device=pyr.device)
+    check(_lib.load().vk_block_flow_u8(_p(pyr), _p(flow), _p(sad), n, H, W, _stream()), "vk_block_flow_u8")
+    return flow, sad
+
+
+def flow_pair_sums(flow, sad, flow_ref=None):
+    """flow (pairs, gy, gx, 2) int16 and sad (pairs, gy, gx, 2) uint16 of block_flow_u8, flow_ref: a second field of flow's shape or None ->
+    (pairs, 5) int64 on the GPU: per pair the blocks with a non-zero vector, sum |v|^2, sum SAD, sum SAD at zero, sum |v - v_ref|^2 (0 without
+    flow_ref) (vk_flow_pair_sums). Nothing is synchronised."""
+    _need(flow, torch.int16, "flow")
+    _need(sad, torch.uint16, "sad")
+    if flow.dim() != 4 or flow.shape[3] != 2 or sad.shape != flow.shape or flow.shape[0] < 1 or flow.shape[1] * flow.shape[2] < 1:
+        raise ValueError(f"flow_pair_sums: expected flow and sad of one shape (pairs, gy, gx, 2), got {tuple(flow.shape)} and {tuple(sad.shape)}")
+    if flow_ref is not None:
+        _need(flow_ref, torch.int16, "flow_ref")
+        if flow_ref.shape != flow.shape:
+            raise ValueError(f"flow_pair_sums: flow is {tuple(flow.shape)}, flow_ref {tuple(flow_ref.shape)}: the two fields must have one shape")
+    for name, t in (("flow", flow), ("sad", sad), ("flow_ref", flow_ref)):
+        if t is not None and t.device != flow.device:
+            raise ValueError(f"flow_pair_sums: flow is on {flow.device}, {name} is on {t.device}")
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"flow_pair_sums: {name} must be dense (contiguous)")
+    aligned = lambda t: t if t is None or t.data_ptr() % 4 == 0 else t.clone()   # noqa: E731
+    flow, sad, flow_ref = aligned(flow), aligned(sad), aligned(flow_ref)
+    pairs, blocks = flow.shape[0], flow.shape[1] * flow.shape[2]
+    out = torch.empty((pairs, 5), dtype=torch.int64, device=flow.device)
+    check(_lib.load().vk_flow_pair_sums(_p(flow), _p(sad), _p(flow_ref), _p(out), pairs, blocks, _stream()), "vk_flow_pair_sums")
+    return out
+
+
 # ---- CLIP-space scores (csrc/perceptual.hip) ----
 EMBED_MAX_ROWS, EMBED_MAX_DIM, EMBED_MMD_TILE = 1 << 20, 1 << 16, 64   # VK_EMBED_* of include/vista_hip.h
 

@@ -100,6 +100,16 @@ def eval_clip():
     return text == "1"
 
 
+def eval_motion():
+    """-> whether `evaluate` adds the motion scores of motion.py (block-matching optical flow) to its records. The one place the environment
+    hook VISTA_EVAL_MOTION is read. Unset or `0`: no, and every record, summary, printed line and file is what was written before the hook
+    existed. `1`: yes. Any other value is refused here, by name, before a model is built."""
+    text = os.environ.get("VISTA_EVAL_MOTION") or "0"
+    if text not in ("0", "1"):
+        raise ValueError(f"Bad value {text} (environment hook VISTA_EVAL_MOTION): 0 or 1")
+    return text == "1"
+
+
 def get_sampler(sampler, steps, discretization_config, guider_config):
     if sampler == "DPMPP2MSampler":
         from .modules.diffusionmodules.sampling import DPMPP2MSampler

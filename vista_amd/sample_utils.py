@@ -200,6 +200,6 @@ def do_sample(images, model, sampler, value_dict, num_rounds, num_frames, force_
 
 # the rest of the reference's sample_utils.py / sample.py helpers (model and sampler factories, dataset lookup, picture I/O) live in
 # vista_amd/pipeline.py; they are exported here because this is where the reference's users look for them
-from .pipeline import (DATASET2SOURCES, SAMPLERS, VERSION2SPECS, check_sizes, eval_clip, get_discretization, get_guider, get_sample, get_sampler,  # noqa: E402,F401
+from .pipeline import (DATASET2SOURCES, SAMPLERS, VERSION2SPECS, check_sizes, eval_clip, eval_motion, get_discretization, get_guider, get_sample, get_sampler,  # noqa: E402,F401
                        init_embedder_options, init_model, init_sampling, load_img, load_img_seq, load_model_from_config,
                        perform_save_locally, png_format, read_video_frames, sampler_name, save_video, video_format)
