@@ -160,6 +160,17 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     return base + slot;
 }
 
+// Counted wait on the wave's vector-memory queue: at most N operations outstanding, i.e. everything but the N youngest has landed (loads retire in
+// order among themselves). The pipelined kernels keep their youngest LDS-DMA pieces in flight across a barrier with it.
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// s_memtime stamp of the timing builds (-DPIPE_TIMING / -DGS_TIMING / -DFF_TIMING: tools/build_variant.sh); the product build has no caller
+__device__ __forceinline__ unsigned long long vk_stamp() {
+    unsigned long long t;
+    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    return t;
+}
+
 // error codes returned by the C-ABI launchers
 #define VK_OK 0
 #define VK_EINVAL (-22)

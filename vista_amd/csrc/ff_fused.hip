@@ -69,25 +69,25 @@ __global__ __launch_bounds__(FF_NT, 2) void ff_fused_kernel(const VkGemmDesc p1,
     float2* const lnrow = (float2*)(smem + OFF_LN);
 
     // ---- per-lane LDS-DMA sources (element offsets; the XOR swizzle of the LDS image lives in the source address) ----
+    using Rows1 = LdsRows<128>;      // W1 slabs
+    using Rows2 = LdsRows<64, 2>;    // W2 chunk and hidden values: 64-byte rows, swizzled by (row >> 2) & 3
     // W1 chunk = five slabs (k = 64 i ..) of [64 rows][128 B]; a 1 KB piece = 8 rows of a slab; DMA wave d (= tgw of an out-projection wave)
     // stages row blocks d and d + 4 of every slab
     const int w1r = 8 * tgw + (lane >> 3);                                     // packed row inside the chunk (first row block); (w1r + 32) >> 1 has the same low bits
-    const int w1off = w1r * FF_C + 8 * ((lane & 7) ^ ((w1r >> 1) & 7));
+    const int w1off = w1r * FF_C + 8 * Rows1::src_chunk(w1r, lane & 7);
     // W2 chunk (chunk-major [chunk][320 rows][32]) = [320 rows][64 B]; a piece = 16 rows; DMA wave d stages pieces d, d + 4, .., d + 16
-    const int w2off = (16 * tgw + (lane >> 2)) * FF_HC + 8 * ((lane & 3) ^ ((lane >> 4) & 3));   // ((row >> 2) & 3) == (lane >> 4) & 3
+    const int w2off = (16 * tgw + (lane >> 2)) * FF_HC + 8 * Rows2::src_chunk(lane >> 2, lane & 3);   // (row 16 tgw + (lane >> 2) swizzles as lane >> 2 does)
 
     // ---- per-lane fragment read offsets ----
-    const int sw = (l31 >> 1) & 7;
     int frag_off[4];
 #pragma unroll
-    for (int k4 = 0; k4 < 4; ++k4) frag_off[k4] = ((k4 * 2 + lh) ^ sw) << 4;
+    for (int k4 = 0; k4 < 4; ++k4) frag_off[k4] = Rows1::frag_off(k4, lh, l31);
     const int w1row_off = l31 * 128;                     // fragment c of the chunk: + 32 c rows = 4096 c bytes
-    const int sw2 = (l31 >> 2) & 3;
     int w2f_off[2], h_off[2];                            // k-substep s of a chunk: W2 fragment rows / this lane's token row of the H slot
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-        w2f_off[s] = l31 * 64 + (((2 * s + lh) ^ sw2) << 4);   // + 32 f rows = 2048 f bytes; ((n >> 2) & 3) == sw2 for every f
-        h_off[s] = (32 * tgw + l31) * 64 + (((2 * s + lh) ^ sw2) << 4);   // written by the in-projection lane (l31, lh) of fragment s, read by the same lane index
+        w2f_off[s] = l31 * 64 + Rows2::frag_off(s, lh, l31);   // + 32 f rows = 2048 f bytes: the same swizzle for every f
+        h_off[s] = (32 * tgw + l31) * 64 + Rows2::frag_off(s, lh, l31);   // written by the in-projection lane (l31, lh) of fragment s, read by the same lane index
     }
 
     // ---- once per workgroup: per-column vectors of the in-projection ----
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(FF_NT, 2) void ff_fused_kernel(const VkGemmDesc p1,
     // DBG & 8: per-phase cycle counts (s_memtime) summed over the tiles of this workgroup, written by lane 0 of every wave of workgroup 0 to
     // p1.splitk_ws as 8 x int64 per wave: in-projection waves {A, B, C, barrier wait, steps}, out-projection waves {MFMA + DMA, barrier wait, steps, epilogue, MFMA + DMA again}
     long long tacc[5] = {0, 0, 0, 0, 0};
-    auto now = [&]() -> long long { return (DBG & 8) ? (long long)__builtin_amdgcn_s_memtime() : 0ll; };
+    auto now = [&]() -> long long { return (DBG & 8) ? (long long)vk_stamp() : 0ll; };
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int m0 = tile * FF_BM;
         // ---------------- prologue: W1(0) -> slot 0 (DMA waves), x fragments (in-projection waves), row statistics (everyone) ----------------
@@ -129,10 +129,7 @@ __global__ __launch_bounds__(FF_NT, 2) void ff_fused_kernel(const VkGemmDesc p1,
             for (int q = 0; q < 10; ++q) dma_piece(q, 0, 0, 0);
         }
         if (p1.ln_stats != nullptr) {
-            for (int r = tid; r < FF_BM; r += FF_NT) {
-                const int m = m0 + r;
-                lnrow[r] = ln_row_stats(p1, m < p1.M ? m : p1.M - 1);
-            }
+            for (int r = tid; r < FF_BM; r += FF_NT) lnrow[r] = ln_row_stats(p1, m0 + r, p1.M);
         }
         __syncthreads();
 
@@ -265,10 +262,7 @@ __global__ __launch_bounds__(FF_NT, 2) void ff_fused_kernel(const VkGemmDesc p1,
         } else {
             // =============================== out-projection waves (also the workgroup's DMA engine) ===============================
             f32x16_t O[10][1];   // out-projection accumulator: 32 tokens x 320 columns
-#pragma unroll
-            for (int f = 0; f < 10; ++f)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) O[f][0][r] = 0.f;
+            zero_acc(O);
             // Step 0: nothing to multiply yet; DMA W1(1) -> W1 slot 1, W2(0) -> W2 slot 0.
             // Step j = 1..nit: out-projection of chunk j - 1 (hidden values in H slot (j - 1) & 1, W2(j - 1) in W2 slot (j - 1) & 1): 20 MFMAs, with
             // this step's DMA -- W1(j + 1) -> W1 slot (j + 1) & 1, W2(j) -> W2 slot j & 1, both last read in step j - 1 -- one piece after each of

@@ -27,7 +27,7 @@
 // Small-M, deep-K LINEAR problems run the largest tile over 2..8 K slices (split-K; fp32 partials in the caller's workspace,
 // fixed-order finishing pass) so that tiles x slices fills the chip.
 // LDS: two stages of (A tile + W tile); rows are 128 B (64 bf16) and the 16-B chunk index is XOR-swizzled
-// with (row>>1)&7 so the ds_read_b128 fragment reads are bank-conflict free. Tiles stream HBM/L2 -> LDS by LDS-DMA
+// (gemm_common.h: LdsRows) so the ds_read_b128 fragment reads are bank-conflict free. Tiles stream HBM/L2 -> LDS by LDS-DMA
 // (global_load_lds_dwordx4; the swizzle, the conv gathers and the zero padding live in the per-lane SOURCE address): tile t+1
 // lands while the MFMAs consume tile t, one barrier per K-step, fragment reads double-buffered in registers where they fit.
 // The MFMA is issued "swapped" (weights are the row/A operand, activations the column/B operand) so that a lane
@@ -104,23 +104,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
     const int l31 = lane & 31, lh = lane >> 5;
     const int lin = xcd_remap(bid, total_wg);
     const int kslice = lin / ntiles, logical = lin - kslice * ntiles;
-    // Tile order. Narrow outputs (tilesN < 8): column tile fastest -- the few column tiles of a row tile run together, share its
-    // activation rows in L2, and the whole weight matrix is L2-resident anyway. Wide outputs (GEGLU: 10-40 column tiles, weights of
-    // 6-26 MB against a 4 MiB L2): panels of GM = 8 row tiles, row tile fastest inside a panel, so the 32 workgroups an XCD runs at a
-    // time form an 8 x 4 block that streams 8 activation + 4 weight K-slices per step instead of 1 + 32 (rocprofv3 FETCH_SIZE of the
-    // level-2 GEGLU: 3.06 GB per launch with the column-fastest order = every tile re-streaming its weight tile through the fabric;
-    // 1.24 GB with the panels; same-box A/B +4-8 % at level 2, +0-2 % at level 1, -2-3 % at level 0 where it is therefore not used).
     int tn, tm;
-    if (tilesN < 8 || (long long)p.N * p.K * 2 <= (3LL << 20)) {  // (weights that fit the L2 are re-read from it whatever the order: level-0 GEGLU)
-        tn = logical % tilesN;
-        tm = logical / tilesN;
-    } else {
-        constexpr int GM = 8;
-        const int panel = logical / (GM * tilesN), r = logical - panel * (GM * tilesN);
-        const int gm = (tilesM - panel * GM < GM) ? tilesM - panel * GM : GM;
-        tm = panel * GM + r % gm;
-        tn = r / gm;
-    }
+    tile_order<8>(logical, tilesM, tilesN, p.N, p.K, tm, tn);
     const int m0 = p.m_begin + tm * BM, n0 = tn * BN;
 
     const uint16_t* __restrict__ Ag = (const uint16_t*)p.A;
@@ -133,9 +118,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
     // ---- per-thread global->LDS staging assignment: chunk lc of rows lr + 32*i ----
     const int lc = tid & 7;
     const int lr = tid >> 3;
-    // LDS-DMA (global_load_lds) writes lane l's 16 B at wave_base + 16*l, i.e. row lr, physical slot lc. To land the
-    // swizzled image (logical chunk c at slot c ^ ((row>>1)&7)) the lane must FETCH logical chunk lc ^ sw instead.
-    const int lsrc = lc ^ ((lr >> 1) & 7);
+    using Rows = LdsRows<128>;
+    const int lsrc = Rows::src_chunk(lr, lc);   // LDS-DMA lands lane l's 16 B at row lr, slot lc
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     const uint16_t* wptr[WP];
@@ -156,35 +140,30 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
             a_y0[i] = m;  // row index, for the second source of a channel-concatenated A
             a_x0[i] = 0;
         } else if (AMODE == AMODE_CONV3X3) {
-            const int hw = p.Hout * p.Wout;
-            const int img = m / hw;
-            const int rem = m - img * hw;
-            const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-            a_y0[i] = oy * p.stride - (p.asym_pad ? 0 : 1);  // asym_pad: padding only below / right of the image
-            a_x0[i] = ox * p.stride - (p.asym_pad ? 0 : 1);
-            aptr[i] = Ag + (size_t)img * p.H * p.Wd * p.Cin + lsrc * 8;
+            const ConvPixel px = conv_pixel(m, p.Hout, p.Wout);
+            const ConvOrigin o = conv_origin(p, px.oy, px.ox);
+            a_y0[i] = o.y0;
+            a_x0[i] = o.x0;
+            aptr[i] = Ag + (size_t)px.img * p.H * p.Wd * p.Cin + lsrc * 8;
         } else if (AMODE == AMODE_CONV3D) {  // 3x3x3 conv over (frames, H, W): m = frame*H*W + oy*W + ox, frame = b*T + t
-            const int hw = p.H * p.Wd;
-            const int fr = m / hw;
-            const int rem = m - fr * hw;
-            const int oy = rem / p.Wd, ox = rem - oy * p.Wd;
-            a_y0[i] = (fr << 12) | oy;              // oy, ox < 4096; frame index and in-clip index packed above them
-            a_x0[i] = ((fr % p.T) << 12) | ox;
+            const ConvPixel px = conv_pixel(m, p.H, p.Wd);   // (img = the frame)
+            a_y0[i] = (px.img << 12) | px.oy;              // oy, ox < 4096; frame index and in-clip index packed above them
+            a_x0[i] = ((px.img % p.T) << 12) | px.ox;
             aptr[i] = Ag + lsrc * 8;
         } else {  // TEMPORAL3: m = (b*T + t)*S + s
             const int fr = m / p.S;
-            a_y0[i] = fr % p.T;  // frame index t
+            a_y0[i] = temporal_frame(p, m);
             a_x0[i] = ((fr / p.T) * p.S + (m - fr * p.S)) * p.Cin + lsrc * 8;  // element offset of (clip b, pixel s) in a halo frame
             aptr[i] = Ag + (size_t)m * p.Cin + lsrc * 8;
         }
     }
 
     const int nk_all = p.K / BK;
-    const int kt0 = (int)((long long)kslice * nk_all / ksplit), kt1 = (int)((long long)(kslice + 1) * nk_all / ksplit);
-    // (tap, channel offset) of the next K-step to stage, for the conv loaders: K-step kt = (channel slab kt / NTAPS, tap kt % NTAPS);
-    // starts at this workgroup's first K-step
+    int kt0, kt1;
+    splitk_slice(kslice, nk_all, ksplit, kt0, kt1);
     constexpr int NTAPS = (AMODE == AMODE_CONV3X3) ? 9 : (AMODE == AMODE_TEMPORAL3) ? 3 : (AMODE == AMODE_CONV3D) ? 27 : 1;
-    int tap = (AMODE == AMODE_DENSE) ? 0 : kt0 % NTAPS, c0 = (AMODE == AMODE_DENSE) ? 0 : (kt0 / NTAPS) * BK;
+    KWalk<NTAPS> kw;   // starts at this workgroup's first K-step
+    kw.start(kt0);
 
     // direct global -> LDS staging of tile kt into `stage` (one 1-KiB global_load_lds_dwordx4 per wave and 8-row group)
     auto dma_tile = [&](int kt, int stage) {
@@ -218,7 +197,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
                     __builtin_amdgcn_global_load_lds((gptr_t)asrc[i], (lptr_t)(sA + i * RPP * 128), 16, 0, 0);
             }
         } else if (AMODE == AMODE_CONV3X3) {
-            const int ky = tap / 3, kx = tap - ky * 3;
+            const int ky = kw.tap / 3, kx = kw.tap - ky * 3;
             const int sh = p.ups - 1;
             const int He = p.H << sh, We = p.Wd << sh;
 #pragma unroll
@@ -226,13 +205,13 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
                 const int iy = a_y0[i] + ky, ix = a_x0[i] + kx;
                 const bool ok = a_ok[i] && iy >= 0 && iy < He && ix >= 0 && ix < We;
                 const int sy = iy >> sh, sx = ix >> sh;
-                const uint16_t* src = ok ? aptr[i] + ((size_t)(sy * p.Wd + sx) * p.Cin + c0) : zsrc;
+                const uint16_t* src = ok ? aptr[i] + ((size_t)(sy * p.Wd + sx) * p.Cin + kw.c0) : zsrc;
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sA + i * RPP * 128), 16, 0, 0);
             }
         } else if (AMODE == AMODE_CONV3D) {
             // tap = kt3*9 + ky*3 + kx; zero padding in time (clip ends) and space (video_model-style Conv3d(k=3, pad=1):
             // vwm/modules/autoencoding/temporal_ae.py:24-37,82-87)
-            const int kt3 = tap / 9, r9 = tap - kt3 * 9;
+            const int kt3 = kw.tap / 9, r9 = kw.tap - kt3 * 9;
             const int ky = r9 / 3, kx = r9 - ky * 3;
 #pragma unroll
             for (int i = 0; i < AP; ++i) {
@@ -240,35 +219,30 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
                 const int t = a_x0[i] >> 12, ox = a_x0[i] & 4095;
                 const int tt = t + kt3 - 1, iy = oy + ky - 1, ix = ox + kx - 1;
                 const bool ok = a_ok[i] && tt >= 0 && tt < p.T && iy >= 0 && iy < p.H && ix >= 0 && ix < p.Wd;
-                const uint16_t* src = ok ? aptr[i] + (((size_t)(fr + kt3 - 1) * p.H + iy) * p.Wd + ix) * p.Cin + c0 : zsrc;
+                const uint16_t* src = ok ? aptr[i] + (((size_t)(fr + kt3 - 1) * p.H + iy) * p.Wd + ix) * p.Cin + kw.c0 : zsrc;
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sA + i * RPP * 128), 16, 0, 0);
             }
         } else {
             // frames before / after the local range come from the neighbour ranks' halo frames ([clips][S][Cin], frame-sharded
             // multi-GPU runs) or are the conv's zero padding at the ends of the window (halo pointer NULL)
-            const int dt = tap - 1;
+            const int dt = kw.tap - 1;
             const uint16_t* hprev = (const uint16_t*)p.halo_prev;
             const uint16_t* hnext = (const uint16_t*)p.halo_next;
 #pragma unroll
             for (int i = 0; i < AP; ++i) {
                 const int t = a_y0[i] + dt;
-                const uint16_t* src = aptr[i] + ((ptrdiff_t)dt * p.S * p.Cin + c0);
-                if (t < 0) src = hprev ? hprev + (a_x0[i] + c0) : zsrc;
-                if (t >= p.T) src = hnext ? hnext + (a_x0[i] + c0) : zsrc;
+                const uint16_t* src = aptr[i] + ((ptrdiff_t)dt * p.S * p.Cin + kw.c0);
+                if (t < 0) src = hprev ? hprev + (a_x0[i] + kw.c0) : zsrc;
+                if (t >= p.T) src = hnext ? hnext + (a_x0[i] + kw.c0) : zsrc;
                 if (!a_ok[i]) src = zsrc;
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sA + i * RPP * 128), 16, 0, 0);
             }
         }
-        if (++tap == NTAPS) { tap = 0; c0 += BK; }
+        kw.next();
     };
 
     f32x16_t acc[FX][FY];
-#pragma unroll
-    for (int i = 0; i < FX; ++i)
-#pragma unroll
-        for (int j = 0; j < FY; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // X = MFMA row operand, Y = MFMA column operand. Normal: X = weights, Y = activations. TRANS: swapped.
     constexpr int MW = FM * 32, NW = FN * 32;  // wave tile extents along m / n
@@ -276,10 +250,9 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
     const int yoff = TR ? wn * NW : wm * MW;
     const int xbase = TR ? 0 : A_BYTES;   // X tile lives in sA (TRANS) or sW
     const int ybase = TR ? A_BYTES : 0;
-    const int sw = (l31 >> 1) & 7;
     int frag_off[4];  // byte offset of k-substep ks inside a row
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) frag_off[ks] = ((ks * 2 + lh) ^ sw) << 4;
+    for (int ks = 0; ks < 4; ++ks) frag_off[ks] = Rows::frag_off(ks, lh, l31);
     const int xrow_off = (xoff + l31) * 128, yrow_off = (yoff + l31) * 128;
 
     // K-step compute with double-buffered fragments: the ds_read_b128s of k-substep ks+1 are issued BEFORE the MFMAs of
@@ -333,13 +306,10 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
     const EpiPlan eplan = (ksplit > 1) ? EpiPlan{false, 0, 1} : epi_plan<EPI, OUT_F32, BM, BN>(p, m0, n0);
     dma_tile(kt0, kt0 & 1);
     if (eplan.fast) epi_stage_vectors<BN, NT>(p, epi_vec, n0, eplan, tid);  // like the row statistics: under the first tile's DMA
+    // row statistics of this tile's activation rows -> LDS. Issued AFTER the first tile's DMA so that both HBM round trips are in
+    // flight together; visible to every wave after the barrier below.
     if (p.ln_stats != nullptr) {
-        // row statistics of this tile's activation rows -> LDS. Issued AFTER the first tile's DMA so that both HBM round trips are in
-        // flight together; visible to every wave after the barrier below.
-        for (int r = tid; r < BM; r += NT) {
-            const int m = m0 + r;
-            lnrow_cur[r] = ln_row_stats(p, m < p.m_end ? m : p.m_end - 1);
-        }
+        for (int r = tid; r < BM; r += NT) lnrow_cur[r] = ln_row_stats(p, m0 + r, p.m_end);
     }
     __syncthreads();
     for (int kt = kt0; kt < nk; ++kt) {
@@ -351,12 +321,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_ke
 
     if constexpr (EPI == EPI_LINEAR) {
         if (ksplit > 1) {  // fp32 partial tile of this K slice -> workspace [kslice][M][N]; splitk_finish_kernel applies the epilogue
-            VkGemmDesc q = p;
-            q.out = (float*)p.splitk_ws + (size_t)kslice * p.M * p.N;
-            q.ldc = p.N;
-            q.bias = nullptr; q.rowvec = nullptr; q.res1 = nullptr; q.res2 = nullptr;
-            q.alpha = 1.f; q.beta = 0.f;
-            q.rowvec2 = nullptr; q.ln_stats = nullptr; q.rowstat_out = nullptr; q.act = 0;
+            const VkGemmDesc q = splitk_partial_desc(p, kslice);
             gemm_epilogue<EPI_LINEAR, true, FX, FY, FM, FN>(q, acc, m0, n0, wm, wn, l31, lh);
             continue;  // (split-K launches are never persistent: one slice-tile per workgroup)
         }
@@ -425,9 +390,7 @@ int launch_cfg(const VkGemmDesc* d, hipStream_t stream, int ksplit = 1) {
     const int tilesN = (d->N + BN - 1) / BN;
     const int tilesM = (d->m_end - d->m_begin + BM - 1) / BM;   // (vk_gemm_bf16 normalised the row range)
     VkGemmDesc desc = *d;
-    // Activation rows that at most 4 column-tiles ever read are streamed with the non-temporal policy: they would only evict the
-    // weight tile every workgroup shares (measured +6-8 % on the K=320 level-0 projections, -5-11 % when 10+ column tiles re-read A).
-    desc.tile_cfg = (desc.tile_cfg & ~32) | ((AMODE == AMODE_DENSE && tilesN <= 4) ? 32 : 0);
+    desc.tile_cfg = (desc.tile_cfg & ~32) | (a_rows_nontemporal(AMODE, tilesN) ? 32 : 0);
     int grid = tilesM * tilesN * ksplit;
     if (EPI == EPI_GEGLU) {  // persistent tile walk (see the kernel): one (two for the 8-wave 128x128 variant) resident workgroup per CU
         const int resident = 256 * ((WM * WN == 16) ? 1 : 2);
@@ -725,7 +688,7 @@ inline int validate(const VkGemmDesc* d) {
                        d->mx8_cols > d->N || (d->ld_mx8 % 16) != 0 || d->ld_mx8 < d->mx8_cols || d->ld_mx8s * 32 < d->mx8_cols ||
                        (((size_t)d->mx8_out) & 15) != 0 || d->rowstat_out || (d->ldc % 8) != 0 || (((size_t)d->out) & 15) != 0 ||
                        (d->amode != AMODE_DENSE) || d->res1 || d->res2 || d->rowvec || d->rowvec2 ||
-                       (unsigned long long)d->M * 2ull * (unsigned)d->ldc >= 0xfffff000ull))  // (what epi_plan needs to take the LDS-staged epilogue)
+                       (unsigned long long)d->M * 2ull * (unsigned)d->ldc >= VK_BUF_LIMIT))  // (what epi_plan needs to take the LDS-staged epilogue)
         return VK_EINVAL;
     // (ABI v7, read by the fp16 build only -- validated in both) columns from alt_cols_from on leave as bf16: LINEAR, 16-bit out, whole fragments, no statistics of the output
     if (d->alt_cols_from != 0 && (d->alt_cols_from < 0 || (d->alt_cols_from % 32) != 0 || d->alt_cols_from >= d->N || d->epi != EPI_LINEAR || d->out_f32 ||

@@ -1,5 +1,6 @@
-// Pieces shared by the bf16 (gemm.hip) and fp8 (gemm_fp8.hip) implicit-GEMM kernels: operand-mode / epilogue enums and the fused
-// epilogue. Included inside each translation unit's own anonymous namespace scope.
+// Pieces shared by the GEMM family (gemm.hip, gemm_pipe.hip, gemm_pipe2.hip, gemm_stream.hip, gemm_fp8.hip, ff_fused.hip): operand-mode / epilogue
+// enums, the rules in front of the epilogue that the kernels must state identically (tile order, LDS swizzle, K walk, pixel decode, split-K,
+// buffer addressing), and the fused epilogues.
 #pragma once
 #include "common.h"
 #include "vista_hip.h"
@@ -48,11 +49,13 @@ __device__ __forceinline__ uint32_t pack_out(float a, float b, const VkGemmDesc&
     return pack_bf16(a, b);
 }
 
-// LayerNorm fold (VkGemmDesc.ln_*): (mean, rstd) of activation row m from the producer's partial sums, summed in slab order. The GEMM
+// LayerNorm fold (VkGemmDesc.ln_*): (mean, rstd) of activation row m from the producer's partial sums, summed in slab order; a row past the
+// launch's bound m_end reads the last row's (a tile's table covers whole tiles; only rows below m_end are ever stored). The GEMM
 // kernel evaluates this ONCE per tile row at kernel start (the HBM latency of the slab reads hides behind the first tile's DMA) and
 // parks the pairs in LDS; the epilogues read them back with ds_read -- reading the slabs from the epilogue itself exposed ~2 us of
 // HBM latency per tile with nothing to overlap it (one workgroup per CU): +15-20 % on the level-0 GEGLU / q|k|v kernels.
-__device__ __forceinline__ float2 ln_row_stats(const VkGemmDesc& p, int m) {
+__device__ __forceinline__ float2 ln_row_stats(const VkGemmDesc& p, int m, int m_end) {
+    if (m >= m_end) m = m_end - 1;
     const float2* __restrict__ st = (const float2*)p.ln_stats;
     float s = 0.f, q = 0.f;
     for (int i = 0; i < p.ln_parts; ++i) {
@@ -64,6 +67,120 @@ __device__ __forceinline__ float2 ln_row_stats(const VkGemmDesc& p, int m) {
     const float mu = s * inv_c;
     return make_float2(mu, rsqrtf(fmaxf(q * inv_c - mu * mu, 0.f) + p.ln_eps));
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Rules that every kernel of the family has to state identically (the bitwise contracts between the kernels -- tile split, split-K finishing
+// pass, the pipelined kernels against the sixteen-wave one -- hold only while they do): each is written here ONCE and the kernels call it.
+// What differs between the kernels -- their address state (pointers, masks + 32-bit offsets, byte offsets) and their pipelines -- stays with them.
+
+// What of an XCD's 4 MiB L2 one operand of a launch may count on staying resident
+constexpr long long L2_FIT_BYTES = 3LL << 20;
+
+// Tile order: logical tile -> (row tile tm, column tile tn). Narrow outputs (tilesN < 8): column tile fastest -- the few column tiles of a row
+// tile run together, share its activation rows in L2, and the whole weight matrix is L2-resident anyway. Wide outputs (GEGLU: 10-40 column tiles,
+// weights of 6-26 MB against a 4 MiB L2): panels of GM row tiles, row tile fastest inside a panel, so the 32 workgroups an XCD runs at a time
+// form a GM x 32 / GM block that streams 8 activation + 4 weight K-slices per step (GM = 8) instead of 1 + 32 (rocprofv3 FETCH_SIZE of the
+// level-2 GEGLU: 3.06 GB per launch with the column-fastest order = every tile re-streaming its weight tile through the fabric; 1.24 GB with
+// the panels; same-box A/B +4-8 % at level 2, +0-2 % at level 1, -2-3 % at level 0 where it is therefore not used: weights that fit the L2 are
+// re-read from it whatever the order). GM = 8 for 256-row tiles, 16 for the 128-row tiles of the two-per-CU kernel.
+template <int GM>
+__device__ __forceinline__ void tile_order(int logical, int tilesM, int tilesN, int N, int K, int& tm, int& tn) {
+    if (tilesN < 8 || (long long)N * K * 2 <= L2_FIT_BYTES) {
+        tn = logical % tilesN;
+        tm = logical / tilesN;
+    } else {
+        const int panel = logical / (GM * tilesN), r = logical - panel * (GM * tilesN);
+        const int gm = (tilesM - panel * GM < GM) ? tilesM - panel * GM : GM;
+        tm = panel * GM + r % gm;
+        tn = r / gm;
+    }
+}
+
+// LDS image of a tile: rows of ROW_BYTES, and the 16-byte chunk c of row r sits at slot c ^ ((r >> SHIFT) & MASK): a swap inside its group of
+// MASK + 1 chunks (128-byte rows: 8 chunks, 64-byte rows: 4; a wider row -- the streaming kernel's 640 bytes -- swizzles every 8-chunk group), so that the
+// ds_read_b128 fragment reads of 32 consecutive rows are bank-conflict free. LDS-DMA writes lane l's 16 bytes at wave_base + 16 l, i.e. a fixed
+// (row, slot) per lane: to land the swizzled image the lane must FETCH logical chunk src_chunk(row, slot) -- the swizzle lives in the DMA's source
+// address -- and a fragment read undoes it in its offset. SHIFT = 1 everywhere except the fused FeedForward's 64-byte W2 / hidden-value rows (2).
+template <int ROW_BYTES, int SHIFT = 1>
+struct LdsRows {
+    static constexpr int MASK = (ROW_BYTES / 16 < 8 ? ROW_BYTES / 16 : 8) - 1;
+    static __device__ __forceinline__ int src_chunk(int row, int c) { return c ^ ((row >> SHIFT) & MASK); }
+    // byte offset inside row `row` of logical chunk c / of k-substep ks of an MFMA operand (lane half lh holds chunk 2 ks + lh; row = the lane's l31)
+    static __device__ __forceinline__ int chunk_off(int row, int c) { return src_chunk(row, c) << 4; }
+    static __device__ __forceinline__ int frag_off(int ks, int lh, int l31) { return chunk_off(l31, ks * 2 + lh); }
+};
+
+// K axis of the implicit-GEMM convolutions: [Cin/64][tap][64] (the weight pack's order: all taps of one 64-channel slab before the next slab), so
+// K-step kt = (channel slab kt / NTAPS, tap kt % NTAPS). The walk holds (tap, channel offset) of the NEXT K-step to stage; STEP = what one slab
+// adds to the offset (BK elements, or BK * 2 bytes). NTAPS = 1 (dense): tap stays 0 and nothing reads c0, so the walk compiles to nothing.
+template <int NTAPS, int STEP = BK>
+struct KWalk {
+    int tap = 0, c0 = 0;
+    __device__ __forceinline__ void start(int kt0) {
+        tap = NTAPS == 1 ? 0 : kt0 % NTAPS;
+        c0 = NTAPS == 1 ? 0 : (kt0 / NTAPS) * STEP;
+    }
+    __device__ __forceinline__ void next() {
+        if (++tap == NTAPS) { tap = 0; c0 += STEP; }
+    }
+};
+
+// Output row -> pixel: m = (img * h + oy) * w + ox over images of h x w pixels (the OUTPUT grid Hout x Wout of CONV3X3, the source grid of
+// UPCONV2X2's class rows, frames of CONV3D); the tap-(0,0) origin of a 3x3 window in the (upsampled) source; row -> frame t of TEMPORAL3 / CONV3D
+struct ConvPixel { int img, oy, ox; };
+__device__ __forceinline__ ConvPixel conv_pixel(int m, int h, int w) {
+    const int hw = h * w;
+    const int img = m / hw;
+    const int rem = m - img * hw;
+    const int oy = rem / w;
+    return {img, oy, rem - oy * w};
+}
+struct ConvOrigin { int y0, x0; };
+__device__ __forceinline__ ConvOrigin conv_origin(const VkGemmDesc& p, int oy, int ox) {
+    const int pad = p.asym_pad ? 0 : 1;  // asym_pad: padding only below / right of the image
+    return {oy * p.stride - pad, ox * p.stride - pad};
+}
+__device__ __forceinline__ int temporal_frame(const VkGemmDesc& p, int m) { return (m / p.S) % p.T; }  // m = (b*T + t)*S + s
+
+// Split-K: slice s of ksplit owns K-steps [s * nk / ksplit, (s + 1) * nk / ksplit); its fp32 partial tile goes to the workspace [slice][M][N]
+// through the general epilogue on a descriptor with everything but the store blanked (gemm.hip's splitk_finish_kernel applies the real one)
+__device__ __forceinline__ void splitk_slice(int kslice, int nk_all, int ksplit, int& kt0, int& kt1) {
+    kt0 = (int)((long long)kslice * nk_all / ksplit);
+    kt1 = (int)((long long)(kslice + 1) * nk_all / ksplit);
+}
+__device__ __forceinline__ VkGemmDesc splitk_partial_desc(const VkGemmDesc& p, int kslice) {
+    VkGemmDesc q = p;
+    q.out = (float*)p.splitk_ws + (size_t)kslice * p.M * p.N;
+    q.ldc = p.N;
+    q.bias = nullptr; q.rowvec = nullptr; q.res1 = nullptr; q.res2 = nullptr;
+    q.alpha = 1.f; q.beta = 0.f;
+    q.rowvec2 = nullptr; q.ln_stats = nullptr; q.rowstat_out = nullptr; q.act = 0;
+    return q;
+}
+
+template <int FX, int FY>
+__device__ __forceinline__ void zero_acc(f32x16_t (&acc)[FX][FY]) {
+#pragma unroll
+    for (int i = 0; i < FX; ++i)
+#pragma unroll
+        for (int j = 0; j < FY; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// Buffer-addressed operands (buffer_load ... lds): a wave-uniform resource per operand, 32-bit per-lane byte offsets. An offset at or past the
+// resource's size reads zeros without touching memory -- rows past M, out-of-image taps and frames outside the window need no clamping -- and
+// VK_BUF_OOB is an offset no resource reaches: the host admits only operands below VK_BUF_LIMIT bytes (also the bound of the LDS-staged
+// epilogues' 32-bit byte offsets, epi_plan; tests/test_operands_cpu.py knows it by its earlier per-kernel name P_LIMIT).
+constexpr unsigned VK_BUF_OOB = 0xffffff00u;
+constexpr unsigned long long VK_BUF_LIMIT = 0xfffff000ull;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
+}
+
+// Host policy: activation rows that at most 4 column tiles ever read are streamed with the non-temporal policy: they would only evict the weight
+// tile every workgroup shares (measured +6-8 % on the K=320 level-0 projections, -5-11 % when 10+ column tiles re-read A).
+inline bool a_rows_nontemporal(int amode, int tilesN) { return amode == AMODE_DENSE && tilesN <= 4; }
 
 template <int EPI, bool OUT_F32, int FX, int FY, int FM, int FN>
 __device__ __forceinline__ void gemm_epilogue(const VkGemmDesc& p, f32x16_t (&acc)[FX][FY], int m0, int n0, int wm, int wn, int l31, int lh,
@@ -321,13 +438,21 @@ struct EpiPlan {
     int nimg;
 };
 
+// The images (row-vector indices) that the rows m0 .. m0 + BM of a tile span, for a launch with row vectors (without: the plan's {0, 1} stands)
+template <int BM>
+__device__ __forceinline__ void tile_images(const VkGemmDesc& p, int m0, int& img0, int& nimg) {
+    const int last = (m0 + BM < p.m_end ? m0 + BM : p.m_end) - 1;
+    img0 = m0 / p.rows_per_vec;
+    nimg = last / p.rows_per_vec - img0 + 1;
+}
+
 template <int EPI, bool OUT_F32, int BM, int BN>
 __device__ __forceinline__ EpiPlan epi_plan(const VkGemmDesc& p, int m0, int n0) {
     EpiPlan e{false, 0, 1};
     if (OUT_F32 || EPI == EPI_TRANS) return e;
     if (n0 + BN > p.N || (p.ldc % 8) != 0 || (((size_t)p.out) & 15) != 0) return e;
     // rows are addressed by 32-bit byte offsets from the (uniform) tensor bases
-    const unsigned long long lim = 0xfffff000ull, rows = (unsigned long long)p.M * 2ull;
+    const unsigned long long lim = VK_BUF_LIMIT, rows = (unsigned long long)p.M * 2ull;
     if (rows * (unsigned)p.ldc >= lim || (p.res1 && rows * (unsigned)p.ld_res1 >= lim) || (p.res2 && rows * (unsigned)p.ld_res2 >= lim)) return e;
     if (p.bias && (((size_t)p.bias) & 15) != 0) return e;
     if (p.ln_stats && (((size_t)p.ln_colsum) & 15) != 0) return e;
@@ -336,9 +461,7 @@ __device__ __forceinline__ EpiPlan epi_plan(const VkGemmDesc& p, int m0, int n0)
     if (p.res2 && ((p.ld_res2 % 8) != 0 || (((size_t)p.res2) & 15) != 0)) return e;
     if (p.rowvec || p.rowvec2) {
         if ((p.ldv % 4) != 0 || (p.rowvec && (((size_t)p.rowvec) & 15) != 0) || (p.rowvec2 && (((size_t)p.rowvec2) & 15) != 0)) return e;
-        const int last = (m0 + BM < p.m_end ? m0 + BM : p.m_end) - 1;
-        e.img0 = m0 / p.rows_per_vec;
-        e.nimg = last / p.rows_per_vec - e.img0 + 1;
+        tile_images<BM>(p, m0, e.img0, e.nimg);
         if (e.nimg > EPI_NI) return e;
     }
     e.fast = true;
@@ -350,7 +473,7 @@ __device__ __forceinline__ EpiPlan epi_plan(const VkGemmDesc& p, int m0, int n0)
 __host__ __device__ inline bool epi_fast_everywhere(const VkGemmDesc& p, int epi, int bm) {
     if (p.out_f32 || epi == EPI_TRANS) return false;
     if ((p.ldc % 8) != 0 || (((size_t)p.out) & 15) != 0) return false;
-    const unsigned long long lim = 0xfffff000ull, rows = (unsigned long long)p.M * 2ull;
+    const unsigned long long lim = VK_BUF_LIMIT, rows = (unsigned long long)p.M * 2ull;
     if (rows * (unsigned)p.ldc >= lim || (p.res1 && rows * (unsigned)p.ld_res1 >= lim) || (p.res2 && rows * (unsigned)p.ld_res2 >= lim)) return false;
     if (p.bias && (((size_t)p.bias) & 15) != 0) return false;
     if (p.ln_stats && (((size_t)p.ln_colsum) & 15) != 0) return false;

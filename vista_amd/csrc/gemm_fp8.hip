@@ -74,11 +74,12 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_fp
 
     const uint8_t* __restrict__ Ag = (const uint8_t*)p.A;
     const uint8_t* __restrict__ Wg = (const uint8_t*)p.Wt;
-    const uint8_t* zsrc = (const uint8_t*)&g_zero16_f8;  // formed once and opaque: see gemm.hip
+    const uint8_t* zsrc = (const uint8_t*)&g_zero16_f8;  // formed once and opaque: left alone the compiler re-derives the address in every K-step
     asm volatile("" : "+s"(zsrc));
 
     const int lc = tid & 7, lr = tid >> 3;
-    const int lsrc = lc ^ ((lr >> 1) & 7);  // logical 16-B chunk this lane fetches so that the swizzled image lands (gemm.hip)
+    using Rows = LdsRows<128>;
+    const int lsrc = Rows::src_chunk(lr, lc);  // logical 16-B chunk this lane fetches so that the swizzled image lands
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // 32-bit byte offsets from the (uniform) tensor bases: half the address registers of per-lane pointers (the entry point checks that
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_fp
 #pragma unroll
     for (int i = 0; i < WP; ++i) woff[i] = (uint32_t)(n0 + lr + RPP * i) * (uint32_t)p.K + lsrc * 16;
     // A-row state. Implicit-GEMM loaders (AMODE_CONV3X3 / AMODE_TEMPORAL3: the ResBlock convolutions on fp8 GroupNorm output): the K axis is
-    // the bf16 kernels' [Cin/64][tap][64] order (gemm.hip), in bytes; a 128-byte K-step covers TWO (slab, tap) units, and since a lane always
+    // the bf16 kernels' [Cin/64][tap][64] order (gemm_common.h: KWalk), in bytes; a 128-byte K-step covers TWO (slab, tap) units, and since a lane always
     // stages the same 16-byte chunk of a row, the unit it works on (first or second of the step) and its 16-channel offset inside the unit
     // are per-lane constants: each lane steps its own (tap, slab) pair by two units per K-step.
     constexpr int NTAPS = (AMODE == AMODE_CONV3X3) ? 9 : (AMODE == AMODE_TEMPORAL3) ? 3 : 1;
@@ -102,15 +103,12 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_fp
             aoff[i] = (uint32_t)m * (uint32_t)p.lda + lsrc * 16;
             a_y0[i] = a_x0[i] = 0;
         } else if (AMODE == AMODE_CONV3X3) {  // stride 1, pad 1
-            const int hw = p.H * p.Wd;
-            const int img = m / hw;
-            const int rem = m - img * hw;
-            const int oy = rem / p.Wd;
-            a_y0[i] = row_ok ? oy - 1 : -(1 << 20);
-            a_x0[i] = rem - oy * p.Wd - 1;
-            aoff[i] = (uint32_t)img * (uint32_t)(hw * p.Cin) + (lsrc & 3) * 16;
+            const ConvPixel px = conv_pixel(m, p.H, p.Wd);
+            a_y0[i] = row_ok ? px.oy - 1 : -(1 << 20);
+            a_x0[i] = px.ox - 1;
+            aoff[i] = (uint32_t)px.img * (uint32_t)(p.H * p.Wd * p.Cin) + (lsrc & 3) * 16;
         } else {  // TEMPORAL3: m = (b*T + t)*S + s, zero padding at the clip ends
-            a_y0[i] = row_ok ? (m / p.S) % p.T : -(1 << 20);
+            a_y0[i] = row_ok ? temporal_frame(p, m) : -(1 << 20);
             a_x0[i] = 0;
             aoff[i] = (uint32_t)m * (uint32_t)p.Cin + (lsrc & 3) * 16;
         }
@@ -160,22 +158,19 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 16) ? 4 : 2) void gemm_fp
     };
 
     f32x16_t acc[FX][FY];
-#pragma unroll
-    for (int i = 0; i < FX; ++i)
-#pragma unroll
-        for (int j = 0; j < FY; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     constexpr int MW = FM * 32, NW = FN * 32;
     const int xoff = wn * NW, yoff = wm * MW;
-    const int sw = (l31 >> 1) & 7;
     const int xrow_off = A_BYTES + (xoff + l31) * 128, yrow_off = (yoff + l31) * 128;
 
+    int frag_off[4];  // byte offset inside a row of the lane's chunk i: 2 i + lh
+#pragma unroll
+    for (int i = 0; i < 4; ++i) frag_off[i] = Rows::frag_off(i, lh, l31);
+    // lane half h holds chunk h of K-block 0 (VGPRs 0-3) and chunk 2+h of K-block 1 (VGPRs 4-7) of the 64-byte slab ks
     auto load_frag = [&](const char* rowp, int ks) {
-        const int c = ks * 4 + lh;  // lane half h holds chunk h of K-block 0 (VGPRs 0-3) and chunk 2+h of K-block 1 (VGPRs 4-7) of the slab
-        const i32x4_t lo = *(const i32x4_t*)(rowp + ((c ^ sw) << 4));
-        const i32x4_t hi = *(const i32x4_t*)(rowp + (((c + 2) ^ sw) << 4));
+        const i32x4_t lo = *(const i32x4_t*)(rowp + frag_off[2 * ks]);
+        const i32x4_t hi = *(const i32x4_t*)(rowp + frag_off[2 * ks + 1]);
         i32x8_t v;
         v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
         v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];

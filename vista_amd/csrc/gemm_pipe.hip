@@ -35,8 +35,6 @@ constexpr int PA_BYTES = PBM * 128, PSTAGE = (PBM + PBN) * 128;
 constexpr int PCAP = 256;                      // what the epilogue sizes its residual ring by: 16 registers per accumulator + the ring must fit the VGPRs
 constexpr int APAR0 = 6 * PAP;                 // first bit of the CONV3X3 upsample parities in the validity word
 typedef unsigned amask_t;                      // (8 * PAP = 32 validity + parity bits)
-constexpr unsigned P_OOB = 0xffffff00u;        // an offset no resource below reaches (host: every operand < P_LIMIT bytes)
-constexpr unsigned long long P_LIMIT = 0xfffff000ull;
 static_assert(PAP + PWP <= PFX * PFY && 8 * PAP <= 32, "the piece schedule issues one piece after each MFMA of the first k-substep");
 
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -70,8 +68,8 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     constexpr bool WALK = (EPI == EPI_GEGLU);   // persistent tile walk (pipe_launch); the LINEAR instantiations are compiled as one tile per workgroup
     __shared__ __attribute__((aligned(16))) char smem[2 * PSTAGE + PBM * 8 + epi_vec_floats(PBN) * 4];
 #ifdef PIPE_TIMING
-    unsigned long long tm_k0, tm_dma = 0, tm_bar = 0, tm_loop = 0, tm_epi = 0, tm_ksteps = 0;
-    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tm_k0) :: "memory");
+    unsigned long long tm_dma = 0, tm_bar = 0, tm_loop = 0, tm_epi = 0, tm_ksteps = 0;
+    const unsigned long long tm_k0 = vk_stamp();
 #endif
 
     const int tilesN = p.N / PBN;
@@ -81,11 +79,9 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, lh = lane >> 5;
-    // tile order: as gemm.hip (column tile fastest unless the weights overflow the L2, then panels of 8 row tiles). The launch is
-    // PERSISTENT: workgroup b walks tiles b, b + gridDim.x, ... (gridDim.x is a multiple of 8 whenever it is smaller than the tile count, so a
-    // workgroup's tiles stay in its XCD's range of the remap)
-    // SPLIT (small-M, deep-K LINEAR problems, as gemm.hip's split-K): workgroup = (K slice, tile), the K slice as the slow index; a slice's
-    // fp32 partial tile goes to the workspace [slice][M][N] and gemm.hip's finishing pass applies the epilogue
+    // The launch is PERSISTENT: workgroup b walks tiles b, b + gridDim.x, ... (gridDim.x is a multiple of 8 whenever it is smaller than the tile
+    // count, so a workgroup's tiles stay in its XCD's range of the remap)
+    // SPLIT (small-M, deep-K LINEAR problems): workgroup = (K slice, tile), the K slice as the slow index
     int kslice = 0;
     int cls = 0;   // UPC: the parity class of this workgroup's tile
     auto tile_of = [&](const int bid, int& tm, int& tn) __attribute__((always_inline)) {
@@ -98,16 +94,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
             if (p.tile_cfg & 8) { cls = logical & 3; logical >>= 2; }
             else { cls = logical / ntiles; logical -= cls * ntiles; }
         }
-        if (tilesN < 8 || (long long)p.N * p.K * 2 <= (3LL << 20)) {
-            tn = logical % tilesN;
-            tm = logical / tilesN;
-        } else {
-            constexpr int GM = 8;
-            const int panel = logical / (GM * tilesN), r = logical - panel * (GM * tilesN);
-            const int gm = (tilesM - panel * GM < GM) ? tilesM - panel * GM : GM;
-            tm = panel * GM + r % gm;
-            tn = r / gm;
-        }
+        tile_order<8>(logical, tilesM, tilesN, p.N, p.K, tm, tn);
         // TEMPORAL3 (round 6): walk the row tiles FRAME-fastest. Rows are (clip, frame, pixel); a tile of frame t reads the same pixels of frames t - 1, t, t + 1,
         // so every 128-byte piece of the input is read by three tiles. In row order those three are a whole frame (S / 256 tiles) apart -- about one tile time on
         // an XCD, during which it streams ~17 MB through its 4 MiB L2 -- and two of the three reads come back from the Infinity Cache / HBM (650-750 ticks of own-DMA
@@ -119,7 +106,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
         if constexpr (AMODE == AMODE_TEMPORAL3) {
             if (p.tile_cfg & 8) return;   // (the row order of rounds 4 / 5; validate() admits no descriptor with the bit, the test stays so that the kernel's code does)
             const int nblk = p.S / PBM;
-            if (nblk * PBM == p.S && p.m_begin == 0 && tilesM == (p.M / p.S) * nblk && (long long)p.S * p.Cin * 2 > (3LL << 20)) {
+            if (nblk * PBM == p.S && p.m_begin == 0 && tilesM == (p.M / p.S) * nblk && (long long)p.S * p.Cin * 2 > L2_FIT_BYTES) {
                 const int per_clip = p.T * nblk, clip = tm / per_clip, r = tm - clip * per_clip;
                 const int j = r / p.T, t = r - j * p.T;
                 tm = clip * per_clip + t * nblk + j;
@@ -127,9 +114,10 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
         }
     };
 
-    // ---- staging assignment: 16-byte chunk lc of tile rows lr + 64 * i; the XOR swizzle lives in the SOURCE chunk index (gemm.hip) ----
+    // ---- staging assignment: 16-byte chunk lc of tile rows lr + 64 * i; the XOR swizzle lives in the SOURCE chunk index ----
+    using Rows = LdsRows<128>;
     const int lc = tid & 7, lr = tid >> 3;
-    const int lsrc = lc ^ ((lr >> 1) & 7);
+    const int lsrc = Rows::src_chunk(lr, lc);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const unsigned voff_w = ((unsigned)lr * (unsigned)p.K + (unsigned)lsrc * 8u) * 2u;
     const unsigned wpass = (unsigned)PRPP * (unsigned)p.K * 2u;   // bytes between the row groups of two weight pieces
@@ -142,21 +130,18 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     auto setup = [&](const int m0, const int n0) __attribute__((always_inline)) {
         // (UPC: the four class packs lie one after another, each padded to ceil256(N) rows as every weight pack is -- N is a multiple of 320 here)
         const size_t wrow0 = UPC ? (size_t)cls * (size_t)((p.N + 255) / 256 * 256) + (size_t)n0 : (size_t)n0;
-        rw = __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.Wt + wrow0 * p.K), 0, (int)((unsigned)PBN * (unsigned)p.K * 2u), 0x00020000);
+        rw = buf_rsrc((const uint16_t*)p.Wt + wrow0 * p.K, (unsigned)PBN * (unsigned)p.K * 2u);
         amask = 0;
         if (AMODE == AMODE_UPCONV2X2) {
             // rows m = (img, i, j) over the source image; tap (dy, dx) reads source pixel (i + a - 1 + dy, j + b - 1 + dx): the lane offset is that of tap
             // (0, 0) (it wraps for a row / column of -1, where it is only ever used with a valid tap's step added), the tap step is uniform
-            const int hw = p.H * p.Wd;
-            ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)((unsigned)p.M * (unsigned)p.Cin * 2u), 0x00020000);
+            ra = buf_rsrc(p.A, (unsigned)p.M * (unsigned)p.Cin * 2u);
 #pragma unroll
             for (int i = 0; i < PAP; ++i) {
                 const int m = m0 + lr + PRPP * i;
-                const int img = m / hw;
-                const int rem = m - img * hw;
-                const int sy = rem / p.Wd, sx = rem - sy * p.Wd;
-                const int y0 = sy + (cls >> 1) - 1, x0 = sx + (cls & 1) - 1;
-                voff_a[i] = ((unsigned)((img * p.H + y0) * p.Wd + x0) * (unsigned)p.Cin + (unsigned)lsrc * 8u) * 2u;
+                const ConvPixel px = conv_pixel(m, p.H, p.Wd);   // (a source pixel)
+                const int y0 = px.oy + (cls >> 1) - 1, x0 = px.ox + (cls & 1) - 1;
+                voff_a[i] = ((unsigned)((px.img * p.H + y0) * p.Wd + x0) * (unsigned)p.Cin + (unsigned)lsrc * 8u) * 2u;
                 unsigned mk = 0;   // per piece 2 row-valid + 2 column-valid bits
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
@@ -167,19 +152,17 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
             }
         } else if (AMODE == AMODE_DENSE) {
             const int rows = (p.m_end - m0 < PBM) ? p.m_end - m0 : PBM;
-            ra = __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.A + (size_t)m0 * p.lda), 0,
-                                                   (int)(((unsigned)(rows - 1) * (unsigned)p.lda + (unsigned)p.K) * 2u), 0x00020000);
+            ra = buf_rsrc((const uint16_t*)p.A + (size_t)m0 * p.lda, ((unsigned)(rows - 1) * (unsigned)p.lda + (unsigned)p.K) * 2u);
             voff_a[0] = ((unsigned)lr * (unsigned)p.lda + (unsigned)lsrc * 8u) * 2u;
         } else if (AMODE == AMODE_CONV3X3) {
             const int hw = p.Hout * p.Wout;
-            ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)((unsigned)(p.M / hw) * (unsigned)(p.H * p.Wd) * (unsigned)p.Cin * 2u), 0x00020000);
+            ra = buf_rsrc(p.A, (unsigned)(p.M / hw) * (unsigned)(p.H * p.Wd) * (unsigned)p.Cin * 2u);
 #pragma unroll
             for (int i = 0; i < PAP; ++i) {
                 const int m = m0 + lr + PRPP * i;
-                const int img = m / hw;
-                const int rem = m - img * hw;
-                const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-                const int y0 = oy * p.stride - (p.asym_pad ? 0 : 1), x0 = ox * p.stride - (p.asym_pad ? 0 : 1);
+                const ConvPixel px = conv_pixel(m, p.Hout, p.Wout);
+                const ConvOrigin o = conv_origin(p, px.oy, px.ox);
+                const int img = px.img, y0 = o.y0, x0 = o.x0;
                 // Fused nearest x2 upsample of the source (ups = 2, stride 1; openaimodel.py:100-102): tap (ky, kx) of output pixel (oy, ox) reads
                 // source pixel ((oy - 1 + ky) >> 1, (ox - 1 + kx) >> 1) = (oy >> 1) - 1 + ((ky + 1 + (oy & 1)) >> 1), likewise in x: the row /
                 // column parities ride in amask's top byte and the lane offset is that of source pixel ((oy >> 1) - 1, (ox >> 1) - 1)
@@ -197,12 +180,12 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
                 amask |= (amask_t)mk << (6 * i);
             }
         } else {  // TEMPORAL3: m = (b*T + t)*S + s over [clips*T][S][Cin]; frames outside the window are the conv's zero padding
-            ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)((unsigned)p.M * (unsigned)p.Cin * 2u), 0x00020000);
+            ra = buf_rsrc(p.A, (unsigned)p.M * (unsigned)p.Cin * 2u);
             voff_a[0] = ((unsigned)(m0 + lr) * (unsigned)p.Cin + (unsigned)lsrc * 8u) * 2u;
 #pragma unroll
             for (int i = 0; i < PAP; ++i) {
                 const int m = m0 + lr + PRPP * i;
-                const int t = (m / p.S) % p.T;
+                const int t = temporal_frame(p, m);
                 if (m < p.m_end) amask |= (amask_t)((t > 0 ? 1u : 0u) | 2u | (t + 1 < p.T ? 4u : 0u)) << (3 * i);
             }
         }
@@ -210,7 +193,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
 
     const int nk_all = p.K / BK;
     int nk = nk_all;        // K-steps of this workgroup (SPLIT: of its slice, set below)
-    int tap = 0, c0b = 0;   // (tap, channel-slab byte offset) of the NEXT K-step to stage (conv loaders: K-step = (slab kt / NTAPS, tap kt % NTAPS))
+    KWalk<NTAPS, BK * 2> kw;   // conv loaders: (tap, channel-slab BYTE offset) of the next K-step to stage
     int kb = 0;             // its byte offset inside a weight row (dense: also inside an activation row)
 
     // piece i (i < 5: 64 weight rows, else 64 activation rows) of the next K-step into `stage`; dma_next() after a K-step's last piece
@@ -227,7 +210,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
             if (NT_A) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)kb, 0, 2);
             else __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)kb, 0, 0);
         } else if (AMODE == AMODE_CONV3X3) {
-            const int ky = tap / 3, kx = tap - ky * 3;
+            const int ky = kw.tap / 3, kx = kw.tap - ky * 3;
             const bool ok = ((amask >> (6 * j + ky)) & (amask >> (6 * j + 3 + kx)) & 1u) != 0;
             unsigned v;
             if (p.ups == 2) {   // (kernel-uniform) per-lane tap offset: the source step of a tap depends on the output pixel's parity
@@ -236,25 +219,23 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
             } else {
                 v = voff_a[j] + (unsigned)((ky * p.Wd + kx) * p.Cin) * 2u;
             }
-            if (!ok) v = P_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)c0b, 0, 0);
+            if (!ok) v = VK_BUF_OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)kw.c0, 0, 0);
         } else if (AMODE == AMODE_UPCONV2X2) {
-            const int dy = tap >> 1, dx = tap & 1;
+            const int dy = kw.tap >> 1, dx = kw.tap & 1;
             const bool ok = ((amask >> (4 * j + dy)) & (amask >> (4 * j + 2 + dx)) & 1u) != 0;
-            const unsigned v = ok ? voff_a[j] + (unsigned)((dy * p.Wd + dx) * p.Cin) * 2u : P_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)c0b, 0, 0);
+            const unsigned v = ok ? voff_a[j] + (unsigned)((dy * p.Wd + dx) * p.Cin) * 2u : VK_BUF_OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)kw.c0, 0, 0);
         } else {
-            const unsigned tapoff = (unsigned)((tap - 1) * p.S * p.Cin) * 2u;
-            const bool ok = ((amask >> (3 * j + tap)) & 1u) != 0;
-            const unsigned v = ok ? voff_a[0] + (unsigned)j * apass + tapoff : P_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)c0b, 0, 0);
+            const unsigned tapoff = (unsigned)((kw.tap - 1) * p.S * p.Cin) * 2u;
+            const bool ok = ((amask >> (3 * j + kw.tap)) & 1u) != 0;
+            const unsigned v = ok ? voff_a[0] + (unsigned)j * apass + tapoff : VK_BUF_OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, v, (unsigned)kw.c0, 0, 0);
         }
     };
     auto dma_next = [&]() __attribute__((always_inline)) {
         kb += BK * 2;
-        if (AMODE != AMODE_DENSE) {
-            if (++tap == NTAPS) { tap = 0; c0b += BK * 2; }
-        }
+        kw.next();
     };
     // q-th piece of a K-step in issue order: the activation pieces first (they are the ones that may come from HBM)
     auto dma_q = [&](const int q, const int stage) __attribute__((always_inline)) { dma_piece(q < PAP ? PWP + q : q - PAP, stage); };
@@ -265,18 +246,17 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     const unsigned pf_voff = ((unsigned)(tid >> 1) * (unsigned)p.lda + (unsigned)(tid & 1) * 32u) * 2u;
     auto prefetch = [&](const bool live) __attribute__((always_inline)) {
         if constexpr (PF) {
-            const unsigned v = live ? pf_voff : P_OOB;   // (rows past M and K-steps past the tile: out of range = no memory access)
+            const unsigned v = live ? pf_voff : VK_BUF_OOB;   // (rows past M and K-steps past the tile: out of range = no memory access)
             asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "+v"(pf_dummy) : "v"(v), "s"(ra), "s"((unsigned)kb) : "memory");
         }
     };
 
     f32x16_t acc[PFX][PFY];
 
-    // fragment addresses: weights rows wn*160 + 32*f + l31 of sW, activation rows wm*64 + 32*f + l31 of sA, k-substep ks = chunk (2*ks + lh) ^ sw
-    const int sw = (l31 >> 1) & 7;
+    // fragment addresses: weights rows wn*160 + 32*f + l31 of sW, activation rows wm*64 + 32*f + l31 of sA
     const int xrow = PA_BYTES + (wn * 160 + l31) * 128, yrow = (wm * (PFY * 32) + l31) * 128;
     auto load_frags = [&](const int stage, const int ks, bf16x8_t* xf, bf16x8_t* yf) __attribute__((always_inline)) {
-        const char* sb = smem + stage * PSTAGE + ((((ks * 2 + lh) ^ sw)) << 4);
+        const char* sb = smem + stage * PSTAGE + Rows::frag_off(ks, lh, l31);
 #pragma unroll
         for (int f = 0; f < PFY; ++f) yf[f] = *(const bf16x8_t*)(sb + yrow + f * 32 * 128);
 #pragma unroll
@@ -310,11 +290,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     // a tile's rows span remain to be found
     auto plan_of = [&](const int m0) __attribute__((always_inline)) {
         EpiPlan e{true, 0, 1};
-        if (EPI == EPI_LINEAR && (p.rowvec || p.rowvec2)) {
-            const int last = (m0 + PBM < p.m_end ? m0 + PBM : p.m_end) - 1;
-            e.img0 = m0 / p.rows_per_vec;
-            e.nimg = last / p.rows_per_vec - e.img0 + 1;
-        }
+        if (EPI == EPI_LINEAR && (p.rowvec || p.rowvec2)) tile_images<PBM>(p, m0, e.img0, e.nimg);
         return e;
     };
     // a tile's epilogue vectors and folded-LayerNorm row statistics -> LDS (issued under the tile's first pieces)
@@ -324,10 +300,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
         if (SPLIT) return;   // (the finishing pass applies the epilogue)
         epi_stage_vectors<PBN, PNT>(p, epi_vec, n0, e, tv);
         if (p.ln_stats != nullptr) {
-            for (int r = tv; r < PBM; r += PNT) {
-                const int m = m0 + r;
-                lnrow[r] = ln_row_stats(p, m < p.m_end ? m : p.m_end - 1);
-            }
+            for (int r = tv; r < PBM; r += PNT) lnrow[r] = ln_row_stats(p, m0 + r, p.m_end);
         }
     };
 
@@ -338,10 +311,11 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     int m0 = p.m_begin + tm * PBM, n0 = tn * PBN;
     setup(m0, n0);
     if (SPLIT) {
-        const int kt0 = (int)((long long)kslice * nk_all / ksplit), kt1 = (int)((long long)(kslice + 1) * nk_all / ksplit);
+        int kt0, kt1;
+        splitk_slice(kslice, nk_all, ksplit, kt0, kt1);
         nk = kt1 - kt0;
         kb = kt0 * BK * 2;
-        if (AMODE != AMODE_DENSE) { tap = kt0 % NTAPS; c0b = (kt0 / NTAPS) * BK * 2; }
+        kw.start(kt0);
     }
     int st = 0;   // stage holding the current K-step
 #pragma unroll
@@ -353,15 +327,9 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
 
     while (true) {
 #ifdef PIPE_TIMING
-        unsigned long long tm_t0;
-        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tm_t0) :: "memory");
+        const unsigned long long tm_t0 = vk_stamp();
 #endif
-#pragma unroll
-        for (int i = 0; i < PFX; ++i)
-#pragma unroll
-            for (int j = 0; j < PFY; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        zero_acc(acc);
         bf16x8_t xa[PFX], ya[PFY], xb[PFX], yb[PFY];
         load_frags(st, 0, xa, ya);
         load_frags(st, 1, xb, yb);
@@ -379,11 +347,11 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
             PIPE_SB();
             mma(xa, ya);
             PIPE_SB();
-#ifdef PIPE_TIMING   // s_memtime stamps around the barrier: own-DMA wait and barrier wait per K-step
-            unsigned long long t1, t2, t3;
-            asm volatile("s_waitcnt lgkmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t1) :: "memory");
-            if (PF) asm volatile("s_waitcnt vmcnt(1)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t2) :: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t2) :: "memory");
+#ifdef PIPE_TIMING   // stamps around the barrier: own-DMA wait and barrier wait per K-step
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const unsigned long long t1 = vk_stamp();
+            if (PF) wait_vmcnt<1>(); else wait_vmcnt<0>();
+            const unsigned long long t2 = vk_stamp();
 #endif
             if constexpr (PF) {   // everything but the youngest operation (the prefetch) has landed; a raw barrier: __syncthreads() would add vmcnt(0)
                 asm volatile("s_waitcnt vmcnt(1)\n s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -391,7 +359,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
             } else
             __syncthreads();   // vmcnt(0): this wave's pieces of K-step kt + 1 have landed; lgkmcnt(0): its reads of stage st are done
 #ifdef PIPE_TIMING
-            asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t3) :: "memory");
+            const unsigned long long t3 = vk_stamp();
             tm_dma += t2 - t1; tm_bar += t3 - t2; ++tm_ksteps;
 #endif
             st ^= 1;
@@ -416,8 +384,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
         mma(xb, yb);
         PIPE_SB();
 #ifdef PIPE_TIMING
-        unsigned long long tm_t1;
-        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tm_t1) :: "memory");
+        const unsigned long long tm_t1 = vk_stamp();
         tm_loop += tm_t1 - tm_t0;
 #endif
 
@@ -429,7 +396,8 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
         if (more) {
             tile_of(nbid, ntm, ntn);
             setup(p.m_begin + ntm * PBM, ntn * PBN);
-            kb = 0; tap = 0; c0b = 0;
+            kb = 0;
+            kw.start(0);
 #pragma unroll
             for (int q = 0; q < PWP + PAP; ++q) dma_q(q, st ^ 1);
             dma_next();
@@ -444,20 +412,13 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
         const int e_wave = te >> 6, e_l31 = te & 31, e_lh = (te >> 5) & 1;
         const int e_wm = e_wave >> 1, e_wn = e_wave & 1;
         const float2* const lnp = p.ln_stats != nullptr ? lnrow : nullptr;
-        if constexpr (SPLIT) {   // fp32 partial tile of this K slice (gemm.hip: gemm_kernel's split-K branch)
-            VkGemmDesc q = p;
-            q.out = (float*)p.splitk_ws + (size_t)kslice * p.M * p.N;
-            q.ldc = p.N;
-            q.bias = nullptr; q.rowvec = nullptr; q.res1 = nullptr; q.res2 = nullptr;
-            q.alpha = 1.f; q.beta = 0.f;
-            q.rowvec2 = nullptr; q.ln_stats = nullptr; q.rowstat_out = nullptr; q.act = 0;
+        if constexpr (SPLIT) {   // fp32 partial tile of this K slice
+            const VkGemmDesc q = splitk_partial_desc(p, kslice);
             gemm_epilogue<EPI_LINEAR, true, PFX, PFY, PFY, 5>(q, acc, m0, n0, e_wm, e_wn, e_l31, e_lh);
         } else if constexpr (EPI == EPI_GEGLU) gemm_epilogue_geglu_lds<PFX, PFY, PFY, 5, PBN>(p, acc, m0, n0, e_wm, e_wn, e_l31, e_lh, lnp, epi_vec);
         else gemm_epilogue_linear_lds<PFX, PFY, PFY, 5, PBN, PCAP, GN_CPG, GN_NRES, UPC>(p, acc, m0, n0, e_wm, e_wn, e_l31, e_lh, tn * 2 + e_wn, lnp, epi_vec, eplan.img0, cls);
 #ifdef PIPE_TIMING
-        unsigned long long tm_t2;
-        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tm_t2) :: "memory");
-        tm_epi += tm_t2 - tm_t1;
+        tm_epi += vk_stamp() - tm_t1;
 #endif
         if (!more) break;
         __syncthreads();   // every wave is done with this tile's vectors / row statistics
@@ -471,8 +432,8 @@ __global__ __launch_bounds__(PNT, 2) void gemm_pipe_kernel(const VkGemmDesc p, c
     if constexpr (PF) asm volatile("" :: "v"(pf_dummy));   // (live until here: see its declaration)
 #ifdef PIPE_TIMING
     if (blockIdx.x == 8 && lane == 0 && p.splitk_ws) {   // per wave: [own-DMA wait, barrier wait, K-steps timed, K-loops, epilogues (+ next tile's setup), kernel] in s_memtime ticks
-        unsigned long long tm_end;
-        asm volatile("s_waitcnt vmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tm_end) :: "memory");
+        wait_vmcnt<0>();
+        const unsigned long long tm_end = vk_stamp();
         float* o = (float*)p.splitk_ws + wave * 8;
         o[0] = (float)tm_dma; o[1] = (float)tm_bar; o[2] = (float)tm_ksteps; o[3] = (float)tm_loop; o[4] = (float)tm_epi; o[5] = (float)(tm_end - tm_k0);
     }
@@ -483,7 +444,7 @@ template <int AMODE, int EPI>
 int pipe_launch(const VkGemmDesc* d, hipStream_t stream, int ksplit) {
     const int tilesN = d->N / PBN, tilesM = (d->m_end - d->m_begin + PBM - 1) / PBM;   // (the caller normalised the row range)
     const int ntiles = tilesM * tilesN;
-    const bool nt_a = (AMODE == AMODE_DENSE && tilesN <= 4);   // as gemm.hip's launch_cfg: activation rows that few column tiles re-read are streamed non-temporally
+    const bool nt_a = a_rows_nontemporal(AMODE, tilesN);
     if constexpr (EPI == EPI_LINEAR) {
         if (ksplit > 1) {   // K slices x tiles; the caller (gemm.hip) runs the finishing pass
             if (nt_a) hipLaunchKernelGGL((gemm_pipe_kernel<AMODE, EPI, AMODE == AMODE_DENSE, true>), dim3(ntiles * ksplit), dim3(PNT), 0, stream, *d, ksplit);
@@ -549,8 +510,8 @@ int upconv_fit(const VkGemmDesc* d) {
     VkGemmDesc q = *d;                 // the output's extent (all 4 M_c rows) with the class problem's rows per image: a 256-row tile of CLASS rows
     q.rows_per_vec = d->H * d->Wd;     // must not span more images than the epilogue stages row vectors for
     if (!epi_fast_everywhere(q, EPI_LINEAR, PBM)) return 0;
-    if ((unsigned long long)PBN * d->K * 2ull >= P_LIMIT) return 0;
-    return ((unsigned long long)(d->M / 4) * d->Cin * 2ull < P_LIMIT) ? 1 : 0;
+    if ((unsigned long long)PBN * d->K * 2ull >= VK_BUF_LIMIT) return 0;
+    return ((unsigned long long)(d->M / 4) * d->Cin * 2ull < VK_BUF_LIMIT) ? 1 : 0;
 }
 
 int upconv_launch(const VkGemmDesc* d, hipStream_t stream) {
@@ -569,17 +530,17 @@ extern "C" int vk_gemm_pipe_fit(const VkGemmDesc* d) {
     if ((d->epi != EPI_LINEAR && d->epi != EPI_GEGLU) || d->out_f32 || (d->N % PBN) != 0 || d->mx8_out || d->A2) return 0;
     if (d->epi == EPI_GEGLU && d->amode != AMODE_DENSE) return 0;
     if (!epi_fast_everywhere(*d, d->epi, PBM)) return 0;   // the kernel carries the LDS-staged epilogues only
-    if ((unsigned long long)PBN * d->K * 2ull >= P_LIMIT) return 0;
-    if (d->amode == AMODE_DENSE) return ((unsigned long long)PBM * d->lda * 2ull < P_LIMIT) ? 1 : 0;
+    if ((unsigned long long)PBN * d->K * 2ull >= VK_BUF_LIMIT) return 0;
+    if (d->amode == AMODE_DENSE) return ((unsigned long long)PBM * d->lda * 2ull < VK_BUF_LIMIT) ? 1 : 0;
     if (d->amode == AMODE_CONV3X3) {
         if (d->ups == 2 && (d->stride != 1 || d->asym_pad)) return 0;   // (the fused nearest x2 upsample comes with stride 1, pad 1 only)
         const long long hw = (long long)d->Hout * d->Wout;
         if (hw <= 0 || (d->M % hw) != 0) return 0;
-        return ((unsigned long long)(d->M / hw) * d->H * d->Wd * d->Cin * 2ull < P_LIMIT) ? 1 : 0;
+        return ((unsigned long long)(d->M / hw) * d->H * d->Wd * d->Cin * 2ull < VK_BUF_LIMIT) ? 1 : 0;
     }
     if (d->amode == AMODE_TEMPORAL3) {
         if (d->halo_prev || d->halo_next) return 0;   // neighbour ranks' halo frames are other tensors: the sixteen-wave kernel's per-lane pointers
-        return ((unsigned long long)d->M * d->Cin * 2ull < P_LIMIT) ? 1 : 0;
+        return ((unsigned long long)d->M * d->Cin * 2ull < VK_BUF_LIMIT) ? 1 : 0;
     }
     return 0;
 }

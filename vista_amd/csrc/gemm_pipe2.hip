@@ -5,7 +5,7 @@
 //     ds_read_b128 per 10 MFMAs), 256-VGPR budget; two workgroups = eight waves per CU = two per SIMD, out of phase with each other: one's
 //     epilogue (stores, residual reads, GEGLU arithmetic -- 30-50 % of a short-K tile, profiles/r04_gemm_pipe.txt section 3) runs under the other's
 //     K-loop, which one 162 KB workgroup per CU cannot do;
-//   * what pays for it is LDS: 80 KB per workgroup. K-steps are 32 deep (64-byte LDS rows, chunk index XOR (row >> 1) & 3), the weight tile
+//   * what pays for it is LDS: 80 KB per workgroup. K-steps are 32 deep (64-byte LDS rows, swizzled over their 4 chunks: LdsRows), the weight tile
 //     (320 rows: L2-resident, short latency) is double-buffered and the activation tile (128 rows: may come from HBM) triple-buffered -- 2 x 20 KB
 //     + 3 x 8 KB = 64 KB + the epilogue vectors / LayerNorm row statistics (14 KB);
 //   * per K-step and wave: five weight pieces of K-step kt + 1 and two activation pieces of K-step kt + 2 (buffer_load ... lds, 1 KB each),
@@ -30,14 +30,10 @@ constexpr int QA_ST = QBM * QROW, QW_ST = QBN * QROW;   // 8192 / 20480 bytes pe
 constexpr int QNA = 3, QNW = 2;                  // ring depths
 constexpr int QAP = QBM / 64, QWP = QBN / 64;    // pieces (64 rows x 64 B = one 16-byte chunk per thread) per K-step: 2 + 5
 constexpr int QFX = 5, QFY = 2;
-constexpr unsigned long long Q_LIMIT = 0xfffff000ull;
-constexpr unsigned Q_OOB = 0xffffff00u;         // an offset no resource below reaches (host: every operand < Q_LIMIT bytes)
 
 typedef __attribute__((address_space(3))) void* qlptr_t;
 
 #define Q_SB() __builtin_amdgcn_sched_barrier(0)
-
-template <int N> __device__ __forceinline__ void q_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int EPI, bool NT_A>
 __global__ __launch_bounds__(QNT, 2) void gemm_pipe2_kernel(const VkGemmDesc p) {
@@ -52,56 +48,41 @@ __global__ __launch_bounds__(QNT, 2) void gemm_pipe2_kernel(const VkGemmDesc p) 
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // tile order as gemm_pipe.hip: column tile fastest unless the weights overflow the L2, then panels of 8 row tiles
     int tm, tn;
-    {
-        const int logical = xcd_remap(blockIdx.x, ntiles);
-        if (tilesN < 8 || (long long)p.N * p.K * 2 <= (3LL << 20)) {
-            tn = logical % tilesN;
-            tm = logical / tilesN;
-        } else {
-            constexpr int GM = 16;
-            const int panel = logical / (GM * tilesN), r = logical - panel * (GM * tilesN);
-            const int gm = (tilesM - panel * GM < GM) ? tilesM - panel * GM : GM;
-            tm = panel * GM + r % gm;
-            tn = r / gm;
-        }
-    }
+    tile_order<16>(xcd_remap(blockIdx.x, ntiles), tilesM, tilesN, p.N, p.K, tm, tn);
     const int m0 = p.m_begin + tm * QBM, n0 = tn * QBN;
 
     // ---- staging assignment: thread t moves the 16-byte chunk lc of piece row lr (64 rows x 4 chunks per piece); the swizzle lives in the SOURCE chunk ----
+    using Rows = LdsRows<QROW>;
     const int lc = tid & 3, lr = tid >> 2;
-    const int lsrc = lc ^ ((lr >> 1) & 3);
+    const int lsrc = Rows::src_chunk(lr, lc);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const unsigned voff_w = ((unsigned)lr * (unsigned)p.K + (unsigned)lsrc * 8u) * 2u;
     const unsigned voff_a = ((unsigned)lr * (unsigned)p.lda + (unsigned)lsrc * 8u) * 2u;
     const unsigned wpass = 64u * (unsigned)p.K * 2u, apass = 64u * (unsigned)p.lda * 2u;
-    const __amdgpu_buffer_rsrc_t rw =
-        __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.Wt + (size_t)n0 * p.K), 0, (int)((unsigned)QBN * (unsigned)p.K * 2u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = buf_rsrc((const uint16_t*)p.Wt + (size_t)n0 * p.K, (unsigned)QBN * (unsigned)p.K * 2u);
     const int rows = (p.m_end - m0 < QBM) ? p.m_end - m0 : QBM;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.A + (size_t)m0 * p.lda), 0,
-                                                                        (int)(((unsigned)(rows - 1) * (unsigned)p.lda + (unsigned)p.K) * 2u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = buf_rsrc((const uint16_t*)p.A + (size_t)m0 * p.lda, ((unsigned)(rows - 1) * (unsigned)p.lda + (unsigned)p.K) * 2u);
     // the pieces of K-step `k` (rows past M: out-of-range offsets, which the hardware returns as zeros). `live` = false turns the piece into an
     // out-of-range read as well (zeros into a stage nobody reads any more): the K-loop issues the same seven pieces in every iteration, so it is
     // straight-line code with ONE counted wait -- a wave-uniform branch around a piece splits the MFMA sequence into basic blocks, and the fragment
     // vectors crossing them came back as v_perm_b32 shuffles between the MFMAs
     auto dma_w = [&](const int i, const int k, const bool live) __attribute__((always_inline)) {
         char* const dst = smem + OFF_W + (k % QNW) * QW_ST + i * 64 * QROW + wave_u * 1024;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (qlptr_t)dst, 16, live ? voff_w : Q_OOB, (unsigned)i * wpass + (unsigned)k * QROW, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (qlptr_t)dst, 16, live ? voff_w : VK_BUF_OOB, (unsigned)i * wpass + (unsigned)k * QROW, 0, 0);
     };
     auto dma_a = [&](const int j, const int k, const bool live) __attribute__((always_inline)) {
         char* const dst = smem + (k % QNA) * QA_ST + j * 64 * QROW + wave_u * 1024;
-        const unsigned v = live ? voff_a + (unsigned)j * apass : Q_OOB;
+        const unsigned v = live ? voff_a + (unsigned)j * apass : VK_BUF_OOB;
         if (NT_A) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (qlptr_t)dst, 16, v, (unsigned)k * QROW, 0, 2);
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (qlptr_t)dst, 16, v, (unsigned)k * QROW, 0, 0);
     };
 
     f32x16_t acc[QFX][QFY];
-    // fragment addresses: weight rows wn*160 + 32 f + l31, activation rows wm*64 + 32 f + l31; k-substep ks = chunk (2 ks + lh) ^ ((row >> 1) & 3)
-    const int sw = (l31 >> 1) & 3;
+    // fragment addresses: weight rows wn*160 + 32 f + l31, activation rows wm*64 + 32 f + l31
     const int xrow = OFF_W + (wn * 160 + l31) * QROW, yrow = (wm * 64 + l31) * QROW;
     auto load_frags = [&](const int k, const int ks, bf16x8_t* xf, bf16x8_t* yf) __attribute__((always_inline)) {
-        const int co = ((ks * 2 + lh) ^ sw) << 4;
+        const int co = Rows::frag_off(ks, lh, l31);
         const char* sa = smem + (k % QNA) * QA_ST + yrow + co;
         const char* sx = smem + (k % QNW) * QW_ST + xrow + co;
 #pragma unroll
@@ -136,12 +117,9 @@ __global__ __launch_bounds__(QNT, 2) void gemm_pipe2_kernel(const VkGemmDesc p) 
 
     float2* const lnrow = (float2*)(smem + OFF_LN);
     float* const epi_vec = (float*)(smem + OFF_EV);
-    EpiPlan eplan{true, 0, 1};
-    if (EPI == EPI_LINEAR && (p.rowvec || p.rowvec2)) {
-        const int last = (m0 + QBM < p.m_end ? m0 + QBM : p.m_end) - 1;
-        eplan.img0 = m0 / p.rows_per_vec;
-        eplan.nimg = last / p.rows_per_vec - eplan.img0 + 1;
-    }
+    int img0 = 0, nimg = 1;
+    if (EPI == EPI_LINEAR && (p.rowvec || p.rowvec2)) tile_images<QBM>(p, m0, img0, nimg);
+    const EpiPlan eplan{true, img0, nimg};
 
     // ---- prologue: A(0), W(0), then the tile's epilogue vectors / row statistics (plain loads), then A(1), W(1), A(2) ----
 #pragma unroll
@@ -153,10 +131,7 @@ __global__ __launch_bounds__(QNT, 2) void gemm_pipe2_kernel(const VkGemmDesc p) 
         asm volatile("" : "+v"(tv));   // (nothing lane-derived of this pass is to live across the K-loop)
         epi_stage_vectors<QBN, QNT>(p, epi_vec, n0, eplan, tv);
         if (p.ln_stats != nullptr) {
-            for (int r = tv; r < QBM; r += QNT) {
-                const int m = m0 + r;
-                lnrow[r] = ln_row_stats(p, m < p.m_end ? m : p.m_end - 1);
-            }
+            for (int r = tv; r < QBM; r += QNT) lnrow[r] = ln_row_stats(p, m0 + r, p.m_end);
         }
     }
 #pragma unroll
@@ -165,20 +140,14 @@ __global__ __launch_bounds__(QNT, 2) void gemm_pipe2_kernel(const VkGemmDesc p) 
     for (int i = 0; i < QWP; ++i) dma_w(i, 1, nk > 1);
 #pragma unroll
     for (int j = 0; j < QAP; ++j) dma_a(j, 2, nk > 2);
-    q_wait_vmcnt<QAP + QWP + QAP>();   // A(0), W(0) have landed when at most the nine pieces issued after them are outstanding
+    wait_vmcnt<QAP + QWP + QAP>();   // A(0), W(0) have landed when at most the nine pieces issued after them are outstanding
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the vector / row-statistics ds_writes)
     __builtin_amdgcn_s_barrier();
 
-#pragma unroll
-    for (int i = 0; i < QFX; ++i)
-#pragma unroll
-        for (int j = 0; j < QFY; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#ifdef PIPE_TIMING   // s_memtime stamps of one wave per SIMD of workgroup 8 (tools/build_variant.sh -DPIPE_TIMING; tools/gemm_pipe2_probe.py prints them)
-    unsigned long long tq_k0, tq_wait = 0, tq_t0, tq_t1, tq_t2;
-    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tq_t0) :: "memory");
-    tq_k0 = tq_t0;
+    zero_acc(acc);
+#ifdef PIPE_TIMING   // stamps of one wave per SIMD of workgroup 8 (tools/build_variant.sh -DPIPE_TIMING; tools/gemm_pipe2_probe.py prints them)
+    unsigned long long tq_wait = 0;
+    const unsigned long long tq_t0 = vk_stamp(), tq_k0 = tq_t0;
 #endif
     bf16x8_t xa[QFX], ya[QFY], xb[QFX], yb[QFY];
     load_frags(0, 0, xa, ya);
@@ -191,15 +160,13 @@ __global__ __launch_bounds__(QNT, 2) void gemm_pipe2_kernel(const VkGemmDesc p) 
         Q_SB();
         // K-step kt + 1 landed for this wave: everything but the two youngest pieces (A(kt + 2), live or not)
 #ifdef PIPE_TIMING
-        unsigned long long tq_a, tq_b;
-        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tq_a) :: "memory");
+        const unsigned long long tq_a = vk_stamp();
 #endif
-        q_wait_vmcnt<QAP>();
+        wait_vmcnt<QAP>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's fragment reads of K-step kt are done
         __builtin_amdgcn_s_barrier();   // ... every wave's: its stages are free, K-step kt + 1 is complete (a raw barrier: __syncthreads() would add vmcnt(0))
 #ifdef PIPE_TIMING
-        asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tq_b) :: "memory");
-        tq_wait += tq_b - tq_a;
+        tq_wait += vk_stamp() - tq_a;
 #endif
         load_frags(kt + 1, 0, xa, ya);
         Q_SB();
@@ -214,7 +181,7 @@ __global__ __launch_bounds__(QNT, 2) void gemm_pipe2_kernel(const VkGemmDesc p) 
     Q_SB();
 
 #ifdef PIPE_TIMING
-    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tq_t1) :: "memory");
+    const unsigned long long tq_t1 = vk_stamp();
 #endif
     int te = tid;
     asm volatile("" : "+v"(te));
@@ -225,7 +192,8 @@ __global__ __launch_bounds__(QNT, 2) void gemm_pipe2_kernel(const VkGemmDesc p) 
     else gemm_epilogue_linear_lds<QFX, QFY, 2, 5, QBN, 256>(p, acc, m0, n0, e_wm, e_wn, e_l31, e_lh, tn * 2 + e_wn, lnp, epi_vec, eplan.img0);
 #ifdef PIPE_TIMING
     if (blockIdx.x == 8 && lane == 0 && p.splitk_ws) {   // per wave: [vmcnt + barrier wait, K-steps, K-loop, epilogue, kernel] in s_memtime ticks
-        asm volatile("s_waitcnt vmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tq_t2) :: "memory");
+        wait_vmcnt<0>();
+        const unsigned long long tq_t2 = vk_stamp();
         float* o = (float*)p.splitk_ws + wave * 8;
         o[0] = (float)tq_wait; o[1] = (float)nk; o[2] = (float)(tq_t1 - tq_t0); o[3] = (float)(tq_t2 - tq_t1); o[4] = (float)(tq_t2 - tq_k0); o[5] = 0.f;
     }
@@ -236,7 +204,7 @@ template <int EPI>
 int pipe2_launch(const VkGemmDesc* d, hipStream_t stream) {
     const int tilesN = d->N / QBN, tilesM = (d->m_end - d->m_begin + QBM - 1) / QBM;
     const int ntiles = tilesM * tilesN;
-    const bool nt_a = tilesN <= 4;   // as gemm_pipe.hip: activation rows that few column tiles re-read are streamed non-temporally
+    const bool nt_a = a_rows_nontemporal(AMODE_DENSE, tilesN);
     if (nt_a) hipLaunchKernelGGL((gemm_pipe2_kernel<EPI, true>), dim3(ntiles), dim3(QNT), 0, stream, *d);
     else hipLaunchKernelGGL((gemm_pipe2_kernel<EPI, false>), dim3(ntiles), dim3(QNT), 0, stream, *d);
     VK_CHECK_LAUNCH();
@@ -250,7 +218,7 @@ extern "C" int vk_gemm_pipe2_fit(const VkGemmDesc* d) {
     if (d->amode != AMODE_DENSE || (d->epi != EPI_LINEAR && d->epi != EPI_GEGLU) || d->out_f32 || (d->N % QBN) != 0 || d->mx8_out || d->A2 || d->gnstat_out) return 0;
     if ((d->K % QBK) != 0 || d->K < 2 * QBK) return 0;
     if (!epi_fast_everywhere(*d, d->epi, QBM)) return 0;   // the kernel carries the LDS-staged epilogues only
-    if ((unsigned long long)QBN * d->K * 2ull >= Q_LIMIT || (unsigned long long)QBM * d->lda * 2ull >= Q_LIMIT) return 0;
+    if ((unsigned long long)QBN * d->K * 2ull >= VK_BUF_LIMIT || (unsigned long long)QBM * d->lda * 2ull >= VK_BUF_LIMIT) return 0;
     return 1;
 }
 

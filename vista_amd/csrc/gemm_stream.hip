@@ -25,18 +25,17 @@ namespace {
 constexpr int GS_K = 320, GS_ROWS = 32, GS_NS = 4, GS_RNS = 3, GS_MAXPARTS = 4;
 constexpr int GS_TILE = GS_ROWS * GS_K * 2;   // 20480 bytes: [32 rows][640 B]
 
-template <int N> __device__ __forceinline__ void gs_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void gs_wait(int n) {  // wave-uniform, 0..8
     switch (n) {
-        case 0: gs_wait_vmcnt<0>(); break;
-        case 1: gs_wait_vmcnt<1>(); break;
-        case 2: gs_wait_vmcnt<2>(); break;
-        case 3: gs_wait_vmcnt<3>(); break;
-        case 4: gs_wait_vmcnt<4>(); break;
-        case 5: gs_wait_vmcnt<5>(); break;
-        case 6: gs_wait_vmcnt<6>(); break;
-        case 7: gs_wait_vmcnt<7>(); break;
-        default: gs_wait_vmcnt<8>(); break;
+        case 0: wait_vmcnt<0>(); break;
+        case 1: wait_vmcnt<1>(); break;
+        case 2: wait_vmcnt<2>(); break;
+        case 3: wait_vmcnt<3>(); break;
+        case 4: wait_vmcnt<4>(); break;
+        case 5: wait_vmcnt<5>(); break;
+        case 6: wait_vmcnt<6>(); break;
+        case 7: wait_vmcnt<7>(); break;
+        default: wait_vmcnt<8>(); break;
     }
 }
 
@@ -52,6 +51,7 @@ struct GsLds {
 template <int NW, bool RES>
 __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void gemm_stream_kernel(const VkGemmDesc p, const int tiles_n) {
     using L = GsLds<NW, RES>;
+    using Rows = LdsRows<GS_K * 2>;   // 640-byte rows (activation tile; the residual tile's NTILE * 2 are the same rule)
     constexpr int NTILE = L::NTILE, RT = L::RT;
     static_assert(L::BYTES <= 163840, "LDS budget");
     __shared__ __attribute__((aligned(16))) char smem[L::BYTES];
@@ -92,14 +92,14 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void gemm_stream_kernel(cons
     int cur_img = -1;
 
     // ---- per-lane DMA geometry: the [32][640 B] tile image is lane-linear; this wave stages pieces w and w + 10 (waves 0..9) ----
-    // LDS byte 1024 q + 16 lane -> row r, physical chunk c' of the row; it must hold logical chunk (c' & ~7) | ((c' & 7) ^ ((r >> 1) & 7))
+    // LDS byte 1024 q + 16 lane -> row r, physical chunk c' of the row; it must hold logical chunk src_chunk(r, c')
     int prow[2], pchunk[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int byte = 1024 * (w + 10 * i) + 16 * lane;
         prow[i] = byte / 640;
         const int cp = (byte - prow[i] * 640) >> 4;
-        pchunk[i] = (cp & ~7) | ((cp & 7) ^ ((prow[i] >> 1) & 7));
+        pchunk[i] = Rows::src_chunk(prow[i], cp);
     }
     const int pa = w < 10 ? 2 : 0, pr = (has_res && w < 10) ? 2 : 0, ps = (w < parts) ? 1 : 0;
     const int pw = pa + pr + ps;   // this wave's LDS-DMA pieces per tile
@@ -135,14 +135,13 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void gemm_stream_kernel(cons
     };
 
     // fragment read offsets inside a tile: row l31, logical chunk 2 ks + lh
-    const int sw = (l31 >> 1) & 7;
     int frag_off[4];
 #pragma unroll
-    for (int k4 = 0; k4 < 4; ++k4) frag_off[k4] = l31 * 640 + (((k4 * 2 + lh) ^ sw) << 4);
+    for (int k4 = 0; k4 < 4; ++k4) frag_off[k4] = l31 * 640 + Rows::frag_off(k4, lh, l31);
     // residual chunks of this lane: logical chunk 4 w + 2 gp + lh of row l31 (8 bf16 each)
     int res_off[2];
 #pragma unroll
-    for (int gp = 0; gp < 2; ++gp) { const int c = 4 * w + 2 * gp + lh; res_off[gp] = l31 * (NTILE * 2) + (((c & ~7) | ((c & 7) ^ sw)) << 4); }
+    for (int gp = 0; gp < 2; ++gp) res_off[gp] = l31 * (NTILE * 2) + Rows::chunk_off(l31, 4 * w + 2 * gp + lh);
 
     const int ntiles_mine = walker < tilesM ? (tilesM - walker + nwalk - 1) / nwalk : 0;
     if (ntiles_mine == 0) return;
@@ -161,8 +160,8 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void gemm_stream_kernel(cons
 
 #ifdef GS_TIMING
     long long tt[4] = {0, 0, 0, 0};
-#define GS_T(i) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); tt[i] += t_ - t0_; t0_ = t_; }
-    long long t0_ = (long long)__builtin_amdgcn_s_memtime();
+#define GS_T(i) { const long long t_ = (long long)vk_stamp(); tt[i] += t_ - t0_; t0_ = t_; }
+    long long t0_ = (long long)vk_stamp();
 #else
 #define GS_T(i)
 #endif
