@@ -20,7 +20,9 @@ dynamics-enhanced error) and `structure` (of the Fourier high-pass term), so tha
 structure. `frame_mse` is the unweighted mean of e per frame. A conditioning frame contributes exactly 0 to every figure, as in the reference's
 replace_cond_frames. With --loss_type l1, e is the absolute error.
 
-Not built: several GPUs (WORLD_SIZE > 1) are refused by name; the natural multi-GPU form is scene i on rank i mod W with a merge of the records.
+Several GPUs: WORLD_SIZE > 1 is refused by name unless the environment hook VISTA_SCENE_RANKS=1 is set; then the k-th scene of the walk is scored
+by rank k mod WORLD_SIZE and rank 0 merges the records and writes the summary, with a last key "ranks" (frontdoor.SceneRanks / RankedRun; README
+"Evaluate on several GPUs": separate processes on one GPU have run, several devices have not, no speed-up has been measured).
 The still IMG dataset is allowed: the loss of a still clip is well defined. Random conditioning-frame choices and gradients are not built.
 """
 import math
@@ -200,27 +202,33 @@ def main(argv=None):
     opt, _unknown = parse_args(prog="python -m vista_amd.denoise_loss").parse_known_args(argv)
     # what cannot run is refused here, before 2.5 billion parameters are built
     check_run(opt, frontdoor.net_params(opt))
-    frontdoor.check_world("denoise_loss", "scene-per-rank scoring with a merge of the records is not built")
-    return _loss_loop(opt)
+    ranks = frontdoor.scene_ranks("denoise_loss", "scene-per-rank scoring with a merge of the records is not built", opt.n_scenes)
+    try:
+        return _loss_loop(opt, ranks.join())
+    finally:
+        ranks.leave()
 
 
-def _loss_loop(opt):
+def _loss_loop(opt, ranks=None):
     """The walk of vista_amd.sample over the dataset with the loss behind every scene."""
-    model = frontdoor.build_model(opt)
-    frontdoor.start_records(opt.save, RECORDS_NAME)
-    records, settings = [], settings_of(opt)
-    for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt, n_scenes=opt.n_scenes):
+    _loss_scenes(opt, ranks or frontdoor.SceneRanks()).finish()
+    return 0
+
+
+def _loss_scenes(opt, ranks):
+    """-> the frontdoor.RankedRun of this rank's scenes of the walk, scored and not yet finished."""
+    model = frontdoor.build_model(opt, ranks.rank)
+    run_, settings = frontdoor.RankedRun(ranks, opt.save, RECORDS_NAME, SUMMARY_NAME, summarize), settings_of(opt)
+    for k, (frame_list, sample_index, _dataset_length, action_dict) in run_.scenes(opt, n_scenes=opt.n_scenes):
         timings = {}
         report = run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames, n_conds=opt.n_conds,
                      cond_aug=opt.cond_aug, n_sigmas=opt.n_sigmas, p_mean=opt.p_mean, p_std=opt.p_std, loss_type=opt.loss_type,
                      weighting=opt.weighting, additional=not opt.no_additional_loss, additional_loss_weight=opt.additional_loss_weight,
                      offset_noise_level=opt.offset_noise_level, noise_seed=opt.noise_seed, timings=timings)
         record = make_record(sample_index, frame_list, report, settings, timings)
-        frontdoor.append_record(opt.save, RECORDS_NAME, record)
-        records.append(record)
-        print(_scene_line(record), flush=True)
-    frontdoor.write_summary(opt.save, SUMMARY_NAME, summarize(records))
-    return 0
+        run_.add(k, record)
+        print(ranks.prefix + _scene_line(record), flush=True)
+    return run_
 
 
 if __name__ == "__main__":

@@ -14,8 +14,14 @@ truth. One JSON line per scene goes to <save>/metrics.jsonl, the means over scen
 to <save>/metrics_summary.json; both files describe this run only. The first --n_conds frames are conditioning frames: listed, and excluded from
 every mean. A mean over frames of which one is identical to its ground truth (infinite PSNR) is infinite, and written as null.
 
-Not built: the IMG dataset (one picture repeated has no future to compare against) and several GPUs (WORLD_SIZE > 1) are refused by name; the
-natural multi-GPU form is scene i on rank i mod W with a merge of the records. LPIPS and FVD are not built: their weights are in no checkpoint.
+Not built: the IMG dataset (one picture repeated has no future to compare against) is refused by name, and so is WORLD_SIZE > 1 without the
+hook below. LPIPS and FVD are not built: their weights are in no checkpoint.
+
+Several GPUs: with the environment hook VISTA_SCENE_RANKS=1 under torch.distributed.run the k-th scene of the walk (for --compare: of
+picture_pairs) is sampled and scored by rank k mod WORLD_SIZE, every rank appends its records to <save>/metrics.jsonl.rank<r>, and after one
+barrier rank 0 writes metrics.jsonl in walk order and the summary, with a last key "ranks" (frontdoor.SceneRanks / RankedRun; README "Evaluate
+on several GPUs"). Every line is the single-process run's apart from the timings. Separate processes on one GPU have run; several devices have
+not, and no speed-up has been measured. Unset (or 0), nothing here changes.
 
 With the environment hook VISTA_EVAL_CLIP=1 the records also hold CLIP-space scores from the checkpoint's own image tower (vista_amd/perceptual.py;
 README "CLIP-space scores"): per scored frame `clip_sim`, `clip_step`, `clip_step_real`, their means over the predicted frames, the scene's
@@ -70,8 +76,9 @@ def check_run(opt, net_params=None):
     frontdoor.check_scene_count(opt)
 
 
-def check_world():
-    frontdoor.check_world("evaluate", "scene-per-rank evaluation with a merge of the records is not built")
+def check_world(n_scenes=0):
+    """-> this process's frontdoor.SceneRanks: a single process, unless the hook VISTA_SCENE_RANKS=1 allows WORLD_SIZE > 1."""
+    return frontdoor.scene_ranks("evaluate", "scene-per-rank evaluation with a merge of the records is not built", n_scenes)
 
 
 def rollout_length(n_frames, n_rounds):
@@ -219,10 +226,18 @@ def picture_pairs(directory):
 
 def compare(opt):
     """--compare DIR: the same records and summary from the saved pictures. The bytes are the ones the online run scored, so are the numbers."""
+    ranks = check_world()
+    try:
+        return _compare(opt, ranks).finish() or 0
+    finally:
+        ranks.leave()
+
+
+def _compare(opt, ranks):
+    """-> the frontdoor.RankedRun of this rank's scenes of picture_pairs (the k-th scene on rank k mod W), scored and not yet finished."""
     import numpy as np
     import torch
     from PIL import Image
-    check_world()
     if not 1 <= opt.n_conds:
         raise ValueError(f"--n_conds {opt.n_conds}: at least one conditioning frame")
     ckpt = None
@@ -241,10 +256,10 @@ def compare(opt):
                         motion.check_size(im.height, im.width, f"--compare {opt.compare} with VISTA_EVAL_MOTION=1: {os.path.basename(path)}")
     if not torch.cuda.is_available():
         raise VistaHipError("evaluate --compare: no GPU is visible; vista_amd runs on the MI355X only (no CPU / eager fallback)")
+    ranks.join()
     clip_run = perceptual.RunScores(perceptual.load_tower(opt.config, ckpt)) if ckpt is not None else None
-    frontdoor.start_records(opt.compare, RECORDS_NAME)
-    records = []
-    for dataset, index, frames in scenes:
+    run = _ranked_run(ranks, opt.compare, clip_run, motion_run)
+    for k, (dataset, index, frames) in run.own(scenes):
         t0 = time.perf_counter()
         stacks = []
         for side in (1, 2):
@@ -258,22 +273,27 @@ def compare(opt):
         t1 = time.perf_counter()
         report = fidelity.frame_metrics(stacks[0], stacks[1])
         timings = {"load": t1 - t0, "metrics": time.perf_counter() - t1}
-        more = {**_clip_stage(clip_run, stacks[0], stacks[1], opt.n_conds, timings), **_motion_stage(motion_run, stacks[0], stacks[1], timings)}
+        more = {**_clip_stage(clip_run, stacks[0], stacks[1], opt.n_conds, timings, k), **_motion_stage(motion_run, stacks[0], stacks[1], timings)}
         record = make_record(index, [frames[0][2]], report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
                              n_frames=opt.n_frames, timings=timings, **more)
-        frontdoor.append_record(opt.compare, RECORDS_NAME, record)
-        records.append(record)
-        print(_scene_line(record), flush=True)
-    frontdoor.write_summary(opt.compare, SUMMARY_NAME, _summary(records, clip_run, motion_run))
-    return 0
+        run.add(k, record)
+        print(ranks.prefix + _scene_line(record), flush=True)
+    return run
 
 
-def _clip_stage(clip_run, pred_u8, real_u8, n_conds, timings):
-    """The CLIP-space stage behind a scene's metrics -> the clip= keyword of make_record ({} without the hook: the call is the parent's)."""
+def _ranked_run(ranks, save_dir, clip_run, motion_run):
+    """The records and the summary of this run; the CLIP embeddings behind the run-level clip_mmd travel to rank 0 beside the records."""
+    return frontdoor.RankedRun(ranks, save_dir, RECORDS_NAME, SUMMARY_NAME, lambda records: _summary(records, clip_run, motion_run),
+                               extra=clip_run, extra_name="clip")
+
+
+def _clip_stage(clip_run, pred_u8, real_u8, n_conds, timings, position=None):
+    """The CLIP-space stage behind a scene's metrics -> the clip= keyword of make_record ({} without the hook: the call is the parent's).
+    position: the scene's place in the walk, which a scene-per-rank run keeps with the scene's embeddings."""
     if clip_run is None:
         return {}
     t0 = time.perf_counter()
-    report = clip_run.scene(pred_u8, real_u8, n_conds)   # (its copies to the host end the stage)
+    report = clip_run.scene(pred_u8, real_u8, n_conds, position)   # (its copies to the host end the stage)
     timings["clip"] = time.perf_counter() - t0
     return {"clip": report}
 
@@ -310,20 +330,28 @@ def main(argv=None):
         return compare(opt)
     # what cannot run is refused here, before 2.5 billion parameters are built
     check_run(opt, frontdoor.net_params(opt))
-    check_world()
-    return _evaluate_loop(opt)
+    ranks = check_world(opt.n_scenes)
+    try:
+        return _evaluate_loop(opt, ranks.join())
+    finally:
+        ranks.leave()
 
 
-def _evaluate_loop(opt):
+def _evaluate_loop(opt, ranks=None):
     """The loop of vista_amd.sample with the metrics stage behind every scene."""
+    _evaluate_scenes(opt, ranks or frontdoor.SceneRanks()).finish()
+    return 0
+
+
+def _evaluate_scenes(opt, ranks):
+    """-> the frontdoor.RankedRun of this rank's scenes of the walk, sampled, scored and not yet finished."""
     import torch
     from . import ops
-    model = frontdoor.build_model(opt)
+    model = frontdoor.build_model(opt, ranks.rank)
     clip_run = perceptual.RunScores(perceptual.find_tower(model)) if SU.eval_clip() else None
     motion_run = motion.RunScores() if SU.eval_motion() else None
-    frontdoor.start_records(opt.save, RECORDS_NAME)
-    records = []
-    for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt, n_scenes=opt.n_scenes):
+    run = _ranked_run(ranks, opt.save, clip_run, motion_run)
+    for k, (frame_list, sample_index, _dataset_length, action_dict) in run.scenes(opt, n_scenes=opt.n_scenes):
         timings = {}
         samples, _samples_z, inputs = sample.run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames,
                                                  n_rounds=opt.n_rounds, n_conds=opt.n_conds, n_steps=opt.n_steps, cfg_scale=opt.cfg_scale,
@@ -344,18 +372,16 @@ def _evaluate_loop(opt):
             pred_m, real_m = ops.frames_to_u8(pred_m, real=False), ops.frames_to_u8(real_m, real=True)
         report = fidelity.frame_metrics(pred_m, real_m)   # (its copy to the host ends the stage)
         timings["metrics"] = time.perf_counter() - t0
-        more = {**_clip_stage(clip_run, pred_m, real_m, opt.n_conds, timings), **_motion_stage(motion_run, pred_m, real_m, timings)}
+        more = {**_clip_stage(clip_run, pred_m, real_m, opt.n_conds, timings, k), **_motion_stage(motion_run, pred_m, real_m, timings)}
         if not opt.no_pictures:
             t0 = time.perf_counter()
             frontdoor.save_pictures(opt.save, opt.dataset, sample_index, virtual=samples, real=real)
             timings["save"] = time.perf_counter() - t0
         record = make_record(sample_index, frame_list, report, seed=opt.seed, action=opt.action, n_conds=opt.n_conds, n_rounds=opt.n_rounds,
                              n_frames=opt.n_frames, timings=timings, **more)
-        frontdoor.append_record(opt.save, RECORDS_NAME, record)
-        records.append(record)
-        print(_scene_line(record), flush=True)
-    frontdoor.write_summary(opt.save, SUMMARY_NAME, _summary(records, clip_run, motion_run))
-    return 0
+        run.add(k, record)
+        print(ranks.prefix + _scene_line(record), flush=True)
+    return run
 
 
 if __name__ == "__main__":

@@ -1,6 +1,7 @@
 """What the command-line front doors share: the walk over a dataset, model construction and the start-up refusals, the records files, the
-first window's value dict and the picture tree. vista_amd.sample, reward, evaluate, drive, plan, denoise_loss and step_sweep keep what is their
-own: flags, refusals, `run`, record contents, summary arithmetic and the scene line.
+scene-per-rank form of a run that walks scenes (SceneRanks, RankedRun), the first window's value dict and the picture tree. vista_amd.sample,
+reward, evaluate, drive, plan, denoise_loss and step_sweep keep what is their own: flags, refusals, `run`, record contents, summary arithmetic
+and the scene line.
 
 The walk's order of draws decides which scenes a --rand_gen run visits and what every scene's noise is: seed, scene lookup, the body's draws
 (the cond_aug noise first), then the walk's own randint. It is written down once, in `walk`.
@@ -152,6 +153,173 @@ def rounded_timings(timings):
 
 def timings_text(timings):
     return ", ".join(f"{k} {v:.2f} s" for k, v in timings.items())
+
+
+# ---- scene-per-rank -------------------------------------------------------------------------------------------------------------------------------
+BARRIER_HOURS = 24   # a rank that is done waits at the barrier for the slowest one: the group's timeout is a run's length, not a collective's
+
+
+class SceneRanks:
+    """This process's place in a scene-per-rank run of evaluate / denoise_loss / step_sweep: the k-th scene the walk yields (k = 0, 1, ...)
+    belongs to rank k % world. `rank` and `world` are plain values: SceneRanks(1, 2) is "rank 1 of 2" with no process group -- join() does
+    nothing and the barrier returns at once, so the caller runs the ranks one after the other and finishes rank 0 last. Only scene_ranks()
+    makes one that is `launched`, from torch.distributed.run's environment, and that one joins a group. world 1 is the single-process run."""
+
+    def __init__(self, rank=0, world=1, launched=False):
+        if not 0 <= rank < world:
+            raise ValueError(f"SceneRanks: rank {rank} of {world}")
+        self.rank, self.world, self.launched, self.joined = int(rank), int(world), bool(launched), False
+
+    @property
+    def split(self):
+        return self.world > 1
+
+    @property
+    def prefix(self):
+        """What a rank puts before its scene lines; nothing for a single process."""
+        return f"[rank {self.rank}] " if self.split else ""
+
+    def owns(self, k):
+        return k % self.world == self.rank
+
+    def join(self):
+        """One rank of a torch.distributed.run job: picks the GPU as join_process_group does (VISTA_FORCE_DEVICE, else LOCAL_RANK) and joins
+        a gloo group, whatever VISTA_DIST_BACKEND says: the group exists for one barrier before the merge, no tensor on a device ever enters
+        it, and RCCL refuses two ranks on one device. A single process joins nothing, nor does a rank that was not launched as one."""
+        if not (self.split and self.launched) or self.joined:
+            return self
+        import datetime
+        import torch.distributed as dist
+        dev = int(os.environ.get("VISTA_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if torch.cuda.is_available():   # (a front door without a GPU is refused where it builds its model)
+            torch.cuda.set_device(dev)
+        dist.init_process_group("gloo", rank=self.rank, world_size=self.world, timeout=datetime.timedelta(hours=BARRIER_HOURS))
+        self.joined = True
+        return self
+
+    def barrier(self):
+        if self.joined:
+            import torch.distributed as dist
+            dist.barrier()
+
+    def leave(self):
+        if self.joined:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+            self.joined = False
+
+
+def scene_ranks(module, not_built, n_scenes=0):
+    """The start-up check of a front door that walks scenes -> its SceneRanks (not joined yet). Without the hook VISTA_SCENE_RANKS this is
+    check_world, word for word. With it: WORLD_SIZE unset or 1 is the single-process run; a larger one is rank RANK of WORLD_SIZE, and a
+    count of scenes below WORLD_SIZE is refused because a rank would have nothing to do."""
+    if not SU.scene_ranks():   # (a bad value is refused by name, here)
+        check_world(module, not_built)
+        return SceneRanks()
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world <= 1:
+        return SceneRanks()
+    if 0 < n_scenes < world:
+        raise ValueError(f"--n_scenes {n_scenes} with WORLD_SIZE {world} (environment hook VISTA_SCENE_RANKS=1): scene k runs on rank k mod "
+                         f"{world}, so ranks {n_scenes} .. {world - 1} would have nothing to do; give --n_scenes {world} or more, or fewer ranks")
+    return SceneRanks(int(os.environ.get("RANK", "0")), world, launched=True)
+
+
+def part_name(name, rank):
+    return f"{name}.rank{rank}"
+
+
+def read_parts(save_dir, name, world, count):
+    """The part files <name>.rank<r> of `world` ranks -> the `count` records in walk order. Every line holds {"k": walk position, "record": ...};
+    position k must occur exactly once, in the file of rank k % world. Anything else is an error that names the rank and the position."""
+    found = {}
+    for rank in range(world):
+        path = os.path.join(save_dir, part_name(name, rank))
+        first = f"position {rank}" if rank < count else "no position"
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"scene-per-rank merge: rank {rank} left no part file {path} (it holds {first} onwards): the run is "
+                                    "incomplete, nothing is merged")
+        with open(path) as f:
+            for line in f.read().splitlines():
+                entry = json.loads(line)
+                k = int(entry["k"])
+                if k in found:
+                    raise ValueError(f"scene-per-rank merge: rank {rank} holds position {k} a second time in {path}" if found[k][0] == rank else
+                                     f"scene-per-rank merge: rank {rank} holds position {k} in {path}, which rank {found[k][0]} holds too")
+                if not (0 <= k < count and k % world == rank):
+                    raise ValueError(f"scene-per-rank merge: rank {rank} holds position {k} in {path}; of {count} positions its own are "
+                                     f"{rank}, {rank + world}, ...")
+                found[k] = (rank, entry["record"])
+    for k in range(count):
+        if k not in found:
+            raise ValueError(f"scene-per-rank merge: rank {k % world} holds no record of position {k} in "
+                             f"{os.path.join(save_dir, part_name(name, k % world))}: the run is incomplete, nothing is merged")
+    return [found[k][1] for k in range(count)]
+
+
+class RankedRun:
+    """The records and the summary of one run of a front door that walks scenes, for a single process and for one rank of several.
+
+    A single process (ranks.world == 1) writes what the front doors always wrote: <records_name> started anew, one line per scene, then
+    <summary_name> from summarize(records). One rank of several starts <records_name>.rank<r> anew and appends {"k": position, "record":
+    record} per scene of its own; finish() waits at the barrier, and rank 0 then reads every part file, starts <records_name> anew with the
+    records in walk order, writes summarize(records) with a last key "ranks", and removes the part files. An incomplete run (read_parts)
+    raises before <records_name> is touched: no summary is written and the part files stay.
+
+    extra: what the summary needs beyond the records (evaluate's CLIP embeddings), as an object with save_part(path) -- called by every
+    rank before the barrier -- and load_parts(paths, in rank order) -- called by rank 0 after it; its files are <records_name>.<extra_name>.rank<r>."""
+
+    def __init__(self, ranks, save_dir, records_name, summary_name, summarize, extra=None, extra_name="extra"):
+        self.ranks, self.save_dir, self.records_name, self.summary_name, self.summarize = ranks, save_dir, records_name, summary_name, summarize
+        self.extra, self.extra_name = extra, f"{records_name}.{extra_name}"
+        self.records, self.count = [], 0
+        self.own_name = part_name(records_name, ranks.rank) if ranks.split else records_name
+        start_records(save_dir, self.own_name)
+
+    def own(self, items):
+        """(k, item) for the items at this rank's positions; every rank consumes the whole iterable, and counts it."""
+        for k, item in enumerate(items):
+            self.count = k + 1
+            if self.ranks.owns(k):
+                yield k, item
+
+    def scenes(self, opt, get_scene=None, n_scenes=0):
+        """(k, scene) for this rank's scenes of walk(). Every rank runs the whole walk -- the seeding, the lookup, the advance -- and the
+        caller's body for its own scenes only: the ranks visit the single-process walk's scenes as long as no body draws from Python's
+        `random` between the walk's seed_everything and its randint (torch's and numpy's generators are free: the walk draws from neither)."""
+        return self.own(walk(opt, get_scene, n_scenes))
+
+    def add(self, k, record):
+        append_record(self.save_dir, self.own_name, {"k": int(k), "record": record} if self.ranks.split else record)
+        self.records.append(record)
+
+    def _extra_paths(self):
+        return [os.path.join(self.save_dir, part_name(self.extra_name, r)) for r in range(self.ranks.world)]
+
+    def finish(self):
+        ranks = self.ranks
+        if not ranks.split:
+            write_summary(self.save_dir, self.summary_name, self.summarize(self.records))
+            return
+        if self.extra is not None:
+            self.extra.save_part(self._extra_paths()[ranks.rank])
+        ranks.barrier()
+        if ranks.rank != 0:
+            return
+        records = read_parts(self.save_dir, self.records_name, ranks.world, self.count)
+        if self.extra is not None:
+            self.extra.load_parts(self._extra_paths())
+        summary = self.summarize(records)
+        summary["ranks"] = ranks.world
+        start_records(self.save_dir, self.records_name)
+        for record in records:
+            append_record(self.save_dir, self.records_name, record)
+        write_summary(self.save_dir, self.summary_name, summary)
+        for r in range(ranks.world):
+            os.remove(os.path.join(self.save_dir, part_name(self.records_name, r)))
+        for path in self._extra_paths() if self.extra is not None else []:
+            os.remove(path)
 
 
 # ---- the first window -----------------------------------------------------------------------------------------------------------------------------

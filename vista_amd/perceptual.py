@@ -157,20 +157,46 @@ def mmd_json(d):
 # ---- one evaluation run ---------------------------------------------------------------------------------------------------------------------
 class RunScores:
     """The CLIP-space side of an evaluation run: scores every scene and keeps the predicted frames' embeddings (4 KB a frame, on the GPU) for
-    the run-level MMD."""
+    the run-level MMD. In a scene-per-rank run (frontdoor.RankedRun) every rank saves its scenes' embeddings with their walk positions
+    (save_part: fp32 on the host) and rank 0 puts all of them back on its GPU in walk order (load_parts): the rows and their order are the
+    single-process run's, and so are the bits of the run-level MMD."""
 
     def __init__(self, tower):
-        self.tower, self.pred, self.real = tower, [], []
+        self.tower, self.pred, self.real, self.positions = tower, [], [], []
 
-    def scene(self, pred_u8, real_u8, n_conds):
-        """Two (n, H, W, 3) uint8 stacks -> the scene's PerceptualReport, its MMD over the predicted (not the conditioning) frames."""
+    def scene(self, pred_u8, real_u8, n_conds, position=None):
+        """Two (n, H, W, 3) uint8 stacks -> the scene's PerceptualReport, its MMD over the predicted (not the conditioning) frames.
+        position: the scene's place in the walk, for a run whose scenes are spread over ranks."""
         e_pred, e_real = embed_frames(self.tower, pred_u8), embed_frames(self.tower, real_u8)
         report = frame_scores(e_pred, e_real)
         if e_pred.shape[0] > n_conds:
             report.mmd = mmd(e_pred[n_conds:], e_real[n_conds:])
             self.pred.append(e_pred[n_conds:])
             self.real.append(e_real[n_conds:])
+            self.positions.append(position)
         return report
+
+    def save_part(self, path):
+        import torch
+        if any(k is None for k in self.positions):
+            raise ValueError("RunScores.save_part: a scene was scored without its walk position")
+        torch.save({"positions": [int(k) for k in self.positions], "pred": [e.cpu() for e in self.pred], "real": [e.cpu() for e in self.real]}, path)
+
+    def load_parts(self, paths):
+        """The part files of ranks 0, 1, ... -> this object keeps every rank's embeddings, on the GPU, in walk order."""
+        import os
+        import torch
+        held = {}
+        for rank, path in enumerate(paths):
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"scene-per-rank merge: rank {rank} left no embeddings file {path}: the run is incomplete, nothing is merged")
+            part = torch.load(path)
+            for k, e_pred, e_real in zip(part["positions"], part["pred"], part["real"]):
+                if k in held:
+                    raise ValueError(f"scene-per-rank merge: rank {rank} holds the embeddings of position {k} in {path}, which are held already")
+                held[k] = (e_pred, e_real)
+        self.positions = sorted(held)
+        self.pred, self.real = ([held[k][side].cuda() for k in self.positions] for side in (0, 1))
 
     def summary(self):
         """-> the `clip=` argument of evaluate.summarize."""

@@ -110,6 +110,17 @@ def eval_motion():
     return text == "1"
 
 
+def scene_ranks():
+    """-> whether `evaluate`, `denoise_loss` and `step_sweep` run scene-per-rank under torch.distributed.run (frontdoor.SceneRanks: the k-th
+    scene of the walk on rank k mod WORLD_SIZE, the records merged by rank 0). The one place the environment hook VISTA_SCENE_RANKS is read.
+    Unset or `0`: no, and WORLD_SIZE > 1 is refused as it was before the hook existed. `1`: yes; with WORLD_SIZE unset or 1 the run is the
+    single-process run. Any other value is refused here, by name, before a model is built."""
+    text = os.environ.get("VISTA_SCENE_RANKS") or "0"
+    if text not in ("0", "1"):
+        raise ValueError(f"Bad value {text} (environment hook VISTA_SCENE_RANKS): 0 or 1")
+    return text == "1"
+
+
 def get_sampler(sampler, steps, discretization_config, guider_config):
     if sampler == "DPMPP2MSampler":
         from .modules.diffusionmodules.sampling import DPMPP2MSampler

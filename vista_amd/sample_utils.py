@@ -202,4 +202,4 @@ def do_sample(images, model, sampler, value_dict, num_rounds, num_frames, force_
 # vista_amd/pipeline.py; they are exported here because this is where the reference's users look for them
 from .pipeline import (DATASET2SOURCES, SAMPLERS, VERSION2SPECS, check_sizes, eval_clip, eval_motion, get_discretization, get_guider, get_sample, get_sampler,  # noqa: E402,F401
                        init_embedder_options, init_model, init_sampling, load_img, load_img_seq, load_model_from_config,
-                       perform_save_locally, png_format, read_video_frames, sampler_name, save_video, video_format)
+                       perform_save_locally, png_format, read_video_frames, sampler_name, save_video, scene_ranks, video_format)

@@ -25,7 +25,10 @@ describe this run only. The table names, for each sampler and budget, the smalle
 larger -- null where none of the budgets swept gets there.
 
 Not measured: quality. The distance to a converged run of the same model says how much of the sampler's own error is left, not how good the
-picture is. Not built: rollouts (--n_rounds must be 1) and several GPUs (WORLD_SIZE > 1), refused by name. The still IMG dataset is allowed.
+picture is. Not built: rollouts (--n_rounds must be 1), refused by name. The still IMG dataset is allowed. Several GPUs: WORLD_SIZE > 1 is refused
+by name unless the environment hook VISTA_SCENE_RANKS=1 is set; then the k-th scene of the walk is swept by rank k mod WORLD_SIZE and rank 0 merges
+the records and writes the summary, with a last key "ranks" and every `seconds` its rank's own (frontdoor.SceneRanks / RankedRun; README "Evaluate on
+several GPUs": separate processes on one GPU have run, several devices have not, no speed-up has been measured).
 """
 import math
 import sys
@@ -250,25 +253,31 @@ def main(argv=None):
     opt, _unknown = parse_args(prog="python -m vista_amd.step_sweep").parse_known_args(argv)
     # what cannot run is refused here, before 2.5 billion parameters are built
     samplers, budgets = check_run(opt, frontdoor.net_params(opt))
-    frontdoor.check_world("step_sweep", "scene-per-rank sweeping with a merge of the records is not built")
-    return _sweep_loop(opt, samplers, budgets)
+    ranks = frontdoor.scene_ranks("step_sweep", "scene-per-rank sweeping with a merge of the records is not built", opt.n_scenes)
+    try:
+        return _sweep_loop(opt, samplers, budgets, ranks.join())
+    finally:
+        ranks.leave()
 
 
-def _sweep_loop(opt, samplers, budgets):
+def _sweep_loop(opt, samplers, budgets, ranks=None):
     """The walk of vista_amd.sample over the dataset with the sweep behind every scene."""
-    model = frontdoor.build_model(opt)
-    frontdoor.start_records(opt.save, RECORDS_NAME)
-    records, settings = [], settings_of(opt)
-    for frame_list, sample_index, _dataset_length, action_dict in frontdoor.walk(opt, n_scenes=opt.n_scenes):
+    _sweep_scenes(opt, samplers, budgets, ranks or frontdoor.SceneRanks()).finish()
+    return 0
+
+
+def _sweep_scenes(opt, samplers, budgets, ranks):
+    """-> the frontdoor.RankedRun of this rank's scenes of the walk, swept and not yet finished."""
+    model = frontdoor.build_model(opt, ranks.rank)
+    run_, settings = frontdoor.RankedRun(ranks, opt.save, RECORDS_NAME, SUMMARY_NAME, summarise), settings_of(opt)
+    for k, (frame_list, sample_index, _dataset_length, action_dict) in run_.scenes(opt, n_scenes=opt.n_scenes):
         report = run(model, frame_list, action_dict, height=opt.height, width=opt.width, n_frames=opt.n_frames, n_conds=opt.n_conds,
                      cfg_scale=opt.cfg_scale, cond_aug=opt.cond_aug, eager=opt.eager, seed=opt.seed, samplers=samplers, budgets=budgets,
                      ref_steps=opt.ref_steps, ref_sampler=opt.ref_sampler)
         record = make_record(sample_index, frame_list, report, settings)
-        frontdoor.append_record(opt.save, RECORDS_NAME, record)
-        records.append(record)
-        print(_scene_line(record), flush=True)
-    frontdoor.write_summary(opt.save, SUMMARY_NAME, summarise(records))
-    return 0
+        run_.add(k, record)
+        print(ranks.prefix + _scene_line(record), flush=True)
+    return run_
 
 
 if __name__ == "__main__":
